@@ -1,6 +1,12 @@
 """Benchmark of the hot path: log-likelihood evaluations / second (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (the headline: metric, value, unit, ms_per_step, ...).  ``--full`` adds everything
+else the benchmark measures and checks -- per-kernel and roofline figures (HIP events on sampled steps of the timed region), the sustained run, streams,
+host-array calls, the other BASELINE configurations, the samplers, the CPU baseline, the oracle checks -- and prints two lines: the complete record, then
+the same reduced to its numbers.  ``--dump-outputs DIR``: what the timed path returned in its last step, as DIR/<name>.npy (float64; rank 0's points;
+inputs are seeded, identical from run to run): ``loglike``, ``logprior``, ``status`` on one rank, ``logposterior``, ``status`` with N > 1.
 
 Workload (BASELINE.json configs[1]): ShapeFit + Kaiser P_ell, ell = (0, 2, 4), 40 k-bins, dense synthetic
 survey-like window (120 x 1200), full 120 x 120 precision; one *step* = one pass of the hot path over a batch of
@@ -9,9 +15,9 @@ survey-like window (120 x 1200), full 120 x 120 precision; one *step* = one pass
 N > 1: one process per GPU.  Launched under ``torchrun`` (RANK / WORLD_SIZE in the environment) each process is one rank; launched plainly
 (``python bench.py --gpus N``) the parent -- which never touches the GPU -- starts the N ranks itself as fresh child processes and relays rank 0's JSON line.
 Walkers are sharded contiguously (weak scaling: 1024 points per rank and step); the log-posteriors are exchanged by RCCL all-gathers issued through the library's
-own C ABI (``dl_comm_*``; asynchronous, bucketed over 8 steps).  The line also carries BASELINE configs[4] as written -- ONE 512-walker ensemble on two config-2
+own C ABI (``dl_comm_*``; asynchronous, bucketed over 8 steps).  With --full the line also carries BASELINE configs[4] as written -- ONE 512-walker ensemble on two config-2
 tracers, sharded over the ranks with a synchronous all-gather per half-step (strong scaling) -- under ``config5_strong``.
-Prints ONE JSON line (rank 0).  Synthetic inputs only; nothing here reads /root/reference.
+Prints from rank 0 only.  Synthetic inputs only; nothing here reads the reference.
 """
 import argparse
 import json
@@ -340,6 +346,20 @@ def timed_steps(step, barrier, steps):
         step()
     barrier()
     return time.perf_counter() - t0
+
+
+def dump_outputs(directory, arrays, limit=64 << 20, seed=0):
+    """``--dump-outputs``: every array of ``arrays`` (name -> one value per point of the batch) as ``directory``/<name>.npy in float64.  Above ``limit`` bytes in all,
+    the same fixed, seeded sample of the points is written of every array, and the sampled point indices beside them (``sample_index.npy``)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    index = None
+    if 8 * n * len(arrays) > limit:
+        index = np.sort(np.random.RandomState(seed).choice(n, limit // (8 * (len(arrays) + 1)), replace=False))
+        arrays = dict({name: a[index] for name, a in arrays.items()}, sample_index=index.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
 
 
 def init_rccl_group(parallel, local_rank, rank, world, timeout=180.):
@@ -872,6 +892,40 @@ def dry_run(rank, world):
         dist.destroy_process_group()
 
 
+def headline_line(args, world, B, elapsed, prewarm_ms, prewarm_steps, collective, group):
+    """The headline: the K timed steps of BASELINE configs[1] (all a plain run reports; ``--full`` adds its other figures to it)."""
+    distributed = group is not None
+    return {'metric': 'log-likelihood evals/sec (full-shape P_ell, 3x40 bins)', 'value': world * B * args.steps / elapsed, 'unit': 'evals/s', 'n_gpus': world, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64',
+            'data': 'synthetic', 'prewarm_ms': prewarm_ms, 'prewarm_steps': prewarm_steps,
+            'config': {'workload': 'BASELINE configs[1]: ShapeFit+Kaiser P_ell ell=(0,2,4) x 40 k-bins, dense window 120x1200 (n_kin=400/ell), 120x120 precision, '
+                                   '{:d} batched param points per GPU per step'.format(B), 'batch_per_gpu': B, 'n_params': 6,
+                       'parallelism': 'walkers x{:d}'.format(world) + (', log-posteriors all-gathered in buckets of {:d} steps'.format(GATHER_EVERY) if distributed else ''),
+                       'collective': collective, 'ranks': group.world if distributed else 1, 'rccl_version': getattr(group, 'rccl_version', None) if distributed else None}}
+
+
+def print_lines(lines, group, backend):
+    """Rank 0 prints the JSON ``lines`` (None on the other ranks) as the last lines of the job's stdout; then the group, if any, is closed."""
+    # RCCL writes its version banner through C stdio: buffered when stdout is a pipe, it would come out AFTER the JSON line, at process exit.  Every rank flushes its
+    # C stdio now, then a barrier, then rank 0 prints: the JSON line is the last line of the job's stdout
+    import ctypes
+    try:
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
+    sys.stdout.flush()
+    if group is not None:
+        group.barrier()
+    for line in lines or []:
+        print(json.dumps(line), flush=True)
+    if group is not None:
+        group.barrier()
+        group.close()
+        if backend != 'rccl':
+            import torch.distributed as dist
+            dist.destroy_process_group()
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument('--gpus', type=int, default=1)
@@ -889,7 +943,12 @@ def main():
     parser.add_argument('--dry-run', action='store_true', help='launcher check without a GPU: start the ranks, form the (gloo) group, exchange, print the line skeleton')
     parser.add_argument('--no-events', action='store_true', help='diagnostic: no HIP events attached to the kernels in the timed region')
     parser.add_argument('--allow-torch-fallback', action='store_true', help="diagnostic: if RCCL through the C ABI (dl_comm_*) fails, go on with torch.distributed's nccl binding instead of failing")
+    parser.add_argument('--full', action='store_true', help='everything besides the headline: per-kernel / roofline figures (events in the timed region), sustained run, streams, host-array '
+                        'calls, other configurations, samplers, CPU baseline, oracle checks (the options above that select among them apply to --full only)')
+    parser.add_argument('--dump-outputs', metavar='DIR', default=None, help="write what the timed path returned in its last step (rank 0's points) as DIR/<name>.npy, float64")
     args = parser.parse_args()
+    if args.steps < 1:
+        parser.error('--steps must be at least 1')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))    # (before anything that could touch HIP is imported)
@@ -955,13 +1014,15 @@ def main():
         from desilike_amd.parallel import BucketedAllGather
         bucket = BucketedAllGather(B, torch.float64, device, steps_per_bucket=GATHER_EVERY, keep=False, group=group, force_collective=force_dist)
     counter = [0]
+    last_posterior = [None]   # N > 1: this rank's slice of the bucket the last step wrote its log-posteriors into (--dump-outputs)
 
     def step():
         slot = counter[0] % nslots
         counter[0] += 1
         if distributed:
             # the path's one real exchange: every rank needs every walker's log-posterior (samplers/base.py:200)
-            ctx.eval_logposterior(thetas[slot], bucket.slot(), status=statuses[slot], stream=stream.cuda_stream)
+            last_posterior[0] = bucket.slot()
+            ctx.eval_logposterior(thetas[slot], last_posterior[0], status=statuses[slot], stream=stream.cuda_stream)
             bucket.advance()
         else:
             ctx.eval_batch(thetas[slot], loglike=loglikes[slot], logprior=logpriors[slot], status=statuses[slot], stream=stream.cuda_stream)
@@ -990,25 +1051,36 @@ def main():
     # profiles/) carries events, on every sixth step: 3 samples at --steps 20 (5 until round 3: the `sustained` leg below runs without events and the two figures are meant
     # to be compared).  A sampled launch costs the step ~5 us (measured at --steps 20: 26.9 - 27.2 us per step with 10 samples, 24.4 - 24.8 us without events;
     # tools/sync_probe.py: the closing synchronisation is not the difference); the other kernels are reported as null.
+    # (the kernel intervals are per-kernel figures: a plain run attaches no events, as --no-events)
+    events = args.full and not args.no_events
     short = args.steps < 100
     only = 'theory' if short else None
     every = max(1, min(25, args.steps // (3 if short else 8)))
-    if not args.no_events: ctx.profile_enable(1, only=only)   # the warm-up steps go through the event path too (its first use allocates: not a sample)
+    if events: ctx.profile_enable(1, only=only)   # the warm-up steps go through the event path too (its first use allocates: not a sample)
     for _ in range(args.warmup):
         step()
     barrier()
     # HIP events attached to the kernels' own dispatch packets on the launch stream (hipExtLaunchKernelGGL: no event records between the kernels), on 8 or more
     # steps of a long timed region, 5 of the driver's 20
-    ctx.profile_enable(0 if args.no_events else every, only=only)
+    ctx.profile_enable(every if events else 0, only=only)
     gc.disable()
     elapsed = timed_steps(step, barrier, args.steps)
     gc.enable()
-    kernel_ms = ctx.profile_read() if not args.no_events else dict(theory=1., window_gemm=1., finalize=1., total=1., event_overhead=0., samples=0, samples_per_kernel={})
+    kernel_ms = ctx.profile_read() if events else dict(theory=1., window_gemm=1., finalize=1., total=1., event_overhead=0., samples=0, samples_per_kernel={})
     ctx.profile_enable(0)
     if distributed:
         elapsed = group.max(elapsed)
 
     assert all(int((st != 0).sum().item()) == 0 for st in statuses), 'non-OK status in the benchmark batch'
+    if args.dump_outputs and rank == 0:
+        slot = (counter[0] - 1) % nslots   # the last timed step's buffers
+        if distributed:
+            outputs = {'logposterior': last_posterior[0].cpu().numpy(), 'status': statuses[slot].cpu().numpy()}
+        else:
+            outputs = {'loglike': loglikes[slot].cpu().numpy(), 'logprior': logpriors[slot].cpu().numpy(), 'status': statuses[slot].cpu().numpy()}
+        dump_outputs(args.dump_outputs, outputs)
+    if not args.full:
+        return print_lines([headline_line(args, world, B, elapsed, prewarm_ms, prewarm_steps, collective, group)] if rank == 0 else None, group, backend)
     gathered_check = None
     if distributed:
         # the exchange, checked end to end (outside the timed region): every rank's log-posteriors of its first batch are all-gathered through the group; every rank must hold
@@ -1067,13 +1139,8 @@ def main():
         # which unit bounds the dominant kernel: the theory kernel issues no MFMA (fp64 VALU: transcendentals, spline evaluation, projection -- its 78.6 TFLOP/s peak
         # equals the fp64 matrix peak); the chi2 GEMM is fp64 MFMA (v_mfma_f64_16x16x4_f64)
         bound = {'theory': 'valu', 'window_gemm': 'mfma', 'finalize': 'latency'}[dominant]
-        result = {'metric': 'log-likelihood evals/sec (full-shape P_ell, 3x40 bins)', 'value': value, 'unit': 'evals/s', 'n_gpus': world, 'steps': args.steps,
-                  'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64',
-                  'data': 'synthetic', 'prewarm_ms': prewarm_ms, 'prewarm_steps': prewarm_steps,
-                  'config': {'workload': 'BASELINE configs[1]: ShapeFit+Kaiser P_ell ell=(0,2,4) x 40 k-bins, dense window 120x1200 (n_kin=400/ell), 120x120 precision, '
-                                         '{:d} batched param points per GPU per step'.format(B), 'batch_per_gpu': B, 'n_params': 6,
-                             'parallelism': 'walkers x{:d}'.format(world) + (', log-posteriors all-gathered in buckets of {:d} steps'.format(GATHER_EVERY) if distributed else ''),
-                             'collective': collective, 'ranks': group.world if distributed else 1, 'rccl_version': getattr(group, 'rccl_version', None) if distributed else None},
+        result = headline_line(args, world, B, elapsed, prewarm_ms, prewarm_steps, collective, group)
+        result.update({
                   'roofline': {'bound': bound, 'bound_detail': {'theory': 'fp64 VALU (no MFMA in this kernel: transcendentals, spline evaluation, projection); peak = 78.6 TFLOP/s fp64 vector',
                                                                  'window_gemm': 'fp64 MFMA (v_mfma_f64_16x16x4_f64), peak = 78.6 TFLOP/s fp64 matrix', 'finalize': 'launch latency'}[dominant],
                                'kernel': kernel_name, 'achieved': achieved, 'peak': PEAK_FP64_TFLOPS, 'unit': 'TFLOP/s', 'frac': achieved / PEAK_FP64_TFLOPS, 'traffic': traffic,
@@ -1086,7 +1153,7 @@ def main():
                                'event_samples': int(kernel_ms.get('samples_per_kernel', {}).get(dominant, kernel_ms.get('samples', 0))),
                                'event_mode': 'the dominant kernel only, every {:d} steps (short run)'.format(every) if short else 'all kernels of a sampled step, every {:d} steps'.format(every)},
                   'kernel_ms': {name: (kernel_ms[name] if kernel_ms[name] > 0. else None) for name in ['theory', 'window_gemm', 'finalize']},
-                  'kernel_frac_of_fp64_peak': {name: flops[name] * per_launch / (kernel_ms[name] * 1e-3) / 1e12 / PEAK_FP64_TFLOPS for name in ['theory', 'window_gemm'] if kernel_ms[name] > 0.}}
+                  'kernel_frac_of_fp64_peak': {name: flops[name] * per_launch / (kernel_ms[name] * 1e-3) / 1e12 / PEAK_FP64_TFLOPS for name in ['theory', 'window_gemm'] if kernel_ms[name] > 0.}})
         if gathered_check is not None: result['gathered_check'] = gathered_check
         if sustained is not None:
             sustained['agrees_with_value_within'] = abs(sustained['value'] / value - 1.)
@@ -1105,27 +1172,9 @@ def main():
             result['cpu_baseline'] = base
     else:
         result = None
-    # RCCL writes its version banner through C stdio: buffered when stdout is a pipe, it would come out AFTER the JSON line, at process exit.  Every rank flushes its
-    # C stdio now, then a barrier, then rank 0 prints: the JSON line is the last line of the job's stdout
-    import ctypes
-    try:
-        ctypes.CDLL(None).fflush(None)
-    except Exception:
-        pass
-    sys.stdout.flush()
-    if distributed:
-        group.barrier()
-    if result is not None:
-        # two lines: the complete record (every leg with its workload description, FLOP accounts, latencies), then -- LAST, the line the driver parses and keeps -- the
-        # same headline with every leg reduced to its numbers (< 4 KB: the driver stores a bounded tail of the output)
-        print(json.dumps(dict(result, record='complete')), flush=True)
-        print(json.dumps(compact_line(result)), flush=True)
-    if distributed:
-        group.barrier()
-        group.close()
-        if backend != 'rccl':
-            import torch.distributed as dist
-            dist.destroy_process_group()
+    # two lines: the complete record (every leg with its workload description, FLOP accounts, latencies), then -- LAST, the line the driver parses and keeps -- the
+    # same headline with every leg reduced to its numbers (< 4 KB: the driver stores a bounded tail of the output)
+    print_lines([dict(result, record='complete'), compact_line(result)] if result is not None else None, group, backend)
 
 
 if __name__ == '__main__':

@@ -260,7 +260,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, DL_BENCH_BACKEND='gloo')
     env.pop('WORLD_SIZE', None); env.pop('RANK', None)
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '16', '--warmup', '4', '--prewarm-ms', '50', '--config5-iterations', '4', '--chains-iterations', '6',
-                          '--sustained-seconds', '0.2', '--no-other-configs', '--no-cpu-baseline'],
+                          '--sustained-seconds', '0.2', '--no-other-configs', '--no-cpu-baseline', '--full'],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     lines = out.stdout.decode().strip().splitlines()
@@ -272,6 +272,31 @@ def test_bench_two_ranks_on_one_gpu():
     assert line['config5_strong']['n_gpus'] == 2
     assert line['chains_weak']['n_gpus'] == 2 and [entry['chains'] for entry in line['chains_weak']['per_k']] == [2, 4, 8]      # chain-parallel sampler: K chains per rank
     assert complete['sustained']['steps'] >= 256
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain ``python bench.py --steps K --warmup W`` times exactly K steps of the headline and prints ONE line; ``--dump-outputs`` writes what the last timed step
+    returned (the same seeded points on every run), checked here against the NumPy oracle."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {key: value for key, value in os.environ.items() if key not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '2', '--prewarm-ms', '20', '--dump-outputs', str(tmp_path)],
+                         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    lines = [line for line in out.stdout.decode().splitlines() if line.startswith('{')]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line['steps'] == 7 and line['warmup'] == 2 and line['unit'] == 'evals/s' and line['higher_is_better'] is True and line['dtype'] == 'f64'
+    assert line['value'] == pytest.approx(1024 / (1e-3 * line['ms_per_step']), rel=1e-9)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ['loglike.npy', 'logprior.npy', 'status.npy']
+    loglike, logprior, status = (np.load(str(tmp_path / name)) for name in ['loglike.npy', 'logprior.npy', 'status.npy'])
+    assert loglike.dtype == logprior.dtype == status.dtype == np.float64 and loglike.shape == logprior.shape == status.shape == (1024,)
+    assert (status == 0).all() and np.isfinite(loglike).all()
+    import bench   # (the repository root is on sys.path: tests/conftest.py)
+    like = bench.make_likelihood(0)
+    theta = bench.sample_theta(like, 1024, seed=42)[:4]
+    ref = bench.oracle_logposterior(like, theta)
+    assert (np.abs(loglike[:4] + logprior[:4] - ref) <= 1e-10 * np.maximum(1., np.abs(ref))).all()
 
 
 def test_config5_as_stated_device_vs_host_driver():

@@ -366,6 +366,21 @@ def test_bench_spawns_its_ranks():
     assert out.returncode == 0 and json.loads(out.stdout.decode().strip().splitlines()[-1])['n_gpus'] == 1
 
 
+def test_bench_dump_outputs(tmp_path):
+    """``bench.py --dump-outputs``: float64 arrays under DIR/<name>.npy; above the size limit the same seeded sample of points of every array, its indices beside them."""
+    import bench   # (the repository root is on sys.path: tests/conftest.py)
+    a, b = np.arange(1000, dtype=np.float64), np.arange(1000, dtype=np.int32) % 3
+    bench.dump_outputs(str(tmp_path / 'all'), {'a': a, 'b': b})
+    assert sorted(p.name for p in (tmp_path / 'all').iterdir()) == ['a.npy', 'b.npy']
+    assert np.array_equal(np.load(str(tmp_path / 'all' / 'a.npy')), a) and np.load(str(tmp_path / 'all' / 'b.npy')).dtype == np.float64
+    for run in ['s1', 's2']:
+        bench.dump_outputs(str(tmp_path / run), {'a': a, 'b': b}, limit=2400)
+    index = np.load(str(tmp_path / 's1' / 'sample_index.npy'))
+    assert len(index) == 100 and np.array_equal(index, np.load(str(tmp_path / 's2' / 'sample_index.npy')))
+    assert sum(p.stat().st_size - 128 for p in (tmp_path / 's1').iterdir()) <= 2400
+    assert np.array_equal(np.load(str(tmp_path / 's1' / 'a.npy')), a[index.astype(int)]) and np.array_equal(np.load(str(tmp_path / 's1' / 'b.npy')), b[index.astype(int)])
+
+
 def test_comm_bootstrap_under_torchrun_and_plain_launch(tmp_path):
     """The 128-byte RCCL id travels from rank 0 to the others over a TCP store: torchrun's own agent store (clients of MASTER_PORT) or, launched plainly
     (bench.py --gpus N), a store rank 0 hosts on MASTER_PORT + 1 -- the two ways the driver may start the ranks."""

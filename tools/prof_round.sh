@@ -10,10 +10,10 @@ mkdir -p "$OUT"
 # the kernel sources these summaries belong to (bench.py::source_hash: figures copied from a committed profile enter the bench line only when this matches the running tree)
 python3 -c "import sys; sys.path.insert(0, '$R'); import bench; print(bench.source_hash())" > $OUT/${TAG}_source_hash.txt
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python3 $R/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
-timeout 300 python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_bench_steps20.json 2>> $OUT/${TAG}_bench.err     # the driver's command
+timeout 600 python3 $R/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout 300 python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_bench_steps20.json 2>> $OUT/${TAG}_bench.err     # the driver's step count
 # --no-host-call: the host-array leg launches ~2000 short (1 / 16 / 256-point) instances of the same kernels; with it the trace and every PMC average are diluted (round-4 verdict)
-B="$R/bench.py --no-cpu-baseline --config5-iterations 0 --no-other-configs --no-streams --no-host-call --chains-iterations 0 --sustained-seconds 0"
+B="$R/bench.py --full --no-cpu-baseline --config5-iterations 0 --no-other-configs --no-streams --no-host-call --chains-iterations 0 --sustained-seconds 0"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o $TAG -- python3 $B --steps 200 --warmup 20 > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o $TAG -- python3 $B --no-events --steps 20 --warmup 5 --prewarm-ms 20 > /dev/null 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o $TAG -- python3 $B --no-events --steps 20 --warmup 5 --prewarm-ms 20 > /dev/null 2>&1
@@ -24,7 +24,7 @@ timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIV
 # BASELINE configs[4]: the device-resident ensemble (per-kernel stats of an ensemble update)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_ens -o $TAG -- python3 $R/tools/time_sampler.py > $OUT/${TAG}_time_sampler.txt 2>/dev/null
 # single-rank RCCL smoke run: the N > 1 code path (bucketed all-gathers on the side stream, in-place all-gather inside the ensemble's half-steps) with real RCCL calls on this 1-GPU box
-DL_BENCH_FORCE_DIST=1 DL_ENS_FORCE_COMM=1 timeout 600 python3 $R/bench.py --no-cpu-baseline > $OUT/${TAG}_bench_single_rank_rccl.json 2>/dev/null
+DL_BENCH_FORCE_DIST=1 DL_ENS_FORCE_COMM=1 timeout 600 python3 $R/bench.py --full --no-cpu-baseline > $OUT/${TAG}_bench_single_rank_rccl.json 2>/dev/null
 # the other BASELINE configurations: configs[2] at SURVEY 8d's size, configs[3] -- timings and the kernel traces that the bench line's `other_configs` fractions are checked against
 timeout 900 python3 $R/tools/time_configs.py > $OUT/${TAG}_time_configs.txt 2>/dev/null
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_cfg -o $TAG -- python3 $R/tools/time_configs.py > /dev/null 2>&1

@@ -62,6 +62,15 @@ SYMBOLS = {
     'dl_mh_run_host': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p]),
     'dl_mh_get_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p]),
     'dl_mh_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
+    'dl_nuts_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_double,
+                                      ctypes.c_uint64, ctypes.c_double, ctypes.c_int32, _c_double_p, _c_double_p]),
+    'dl_nuts_destroy': (None, [ctypes.c_void_p]),
+    'dl_nuts_set_mass': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int32, ctypes.c_double, ctypes.c_void_p]),
+    'dl_nuts_set_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
+    'dl_nuts_get_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), _c_double_p, ctypes.c_void_p]),
+    'dl_nuts_set_adaptation': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    'dl_nuts_run': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_nuts_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
     'dl_mlp_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int32, _c_int32_p, ctypes.c_int32, _c_double_p]),
     'dl_mlp_destroy': (None, [ctypes.c_void_p]),
     'dl_mlp_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
@@ -729,6 +738,89 @@ class DeviceMH(object):
     def close(self):
         if getattr(self, '_handle', None):
             self._lib.dl_mh_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceNUTS(object):
+    """Owner of one ``dl_nuts`` (include/desilike_amd.h): ``nchains`` No-U-Turn chains resident on the GPU of ``ctx``, advanced one leapfrog step per call of the
+    gradient.  ``gradient``: 'auto', 'analytic' or 'finite'; ``fd_delta`` / ``fd_limits`` [P, 2]: steps and prior bounds of the central differences."""
+    MODES = {'auto': 0, 'analytic': 1, 'finite': 2}
+
+    def __init__(self, ctx, nchains, chain_ids=None, max_num_doublings=10, divergence_threshold=1000., seed=0, offset=0., gradient='auto', fd_delta=None, fd_limits=None):
+        lib = load()
+        if ctx.expand is not None:
+            raise NotImplementedError('the device-resident sampler moves in the columns of the device context: parameters derived by an expression need the host-driven sampler')
+        P = ctx.n_params
+        chain_ids = np.ascontiguousarray(np.arange(nchains) if chain_ids is None else chain_ids, dtype='i4')
+        if len(chain_ids) != nchains: raise ValueError('chain_ids must have one entry per chain')
+        fd_delta = None if fd_delta is None else np.ascontiguousarray(fd_delta, dtype='f8').reshape(P, 2)
+        fd_limits = None if fd_limits is None else np.ascontiguousarray(fd_limits, dtype='f8').reshape(P, 2)
+        handle = ctypes.c_void_p()
+        if lib.dl_nuts_create(ctypes.byref(handle), ctx._handle, int(nchains), chain_ids.ctypes.data_as(_c_int32_p), int(max_num_doublings), float(divergence_threshold),
+                              ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), float(offset), self.MODES[gradient], _f64_ptr(fd_delta), _f64_ptr(fd_limits)) != 0:
+            raise LibraryError(lib.dl_last_error(None).decode())
+        self._lib, self._handle, self._ctx = lib, handle, ctx     # (the context must outlive the sampler)
+        self.nchains, self.n_params, self.device = int(nchains), P, ctx.device
+
+    def _check(self, rc):
+        if rc != 0:
+            raise LibraryError(self._lib.dl_last_error(None).decode())
+
+    def info(self, key):
+        return int(self._lib.dl_nuts_info(self._handle, key.encode()))
+
+    def _stream(self, stream):
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream(torch.device('cuda', self.device)).cuda_stream if stream is None else stream)
+
+    def set_mass(self, inverse_mass, step_size, stream=None):
+        """Inverse mass matrix: its diagonal [P] or the matrix [P, P]; the step size of every chain."""
+        minv = np.ascontiguousarray(inverse_mass, dtype='f8')
+        if minv.shape not in [(self.n_params,), (self.n_params,) * 2]: raise ValueError('inverse_mass must have shape ({0:d},) or ({0:d}, {0:d})'.format(self.n_params))
+        self._check(self._lib.dl_nuts_set_mass(self._handle, _f64_ptr(minv), int(minv.ndim == 2), float(step_size), self._stream(stream)))
+
+    def set_state(self, coords, logposterior=None, iterations=None, stream=None):
+        coords = np.ascontiguousarray(coords, dtype='f8')
+        if coords.shape != (self.nchains, self.n_params):
+            raise ValueError('coords must have shape ({:d}, {:d}), found {}'.format(self.nchains, self.n_params, coords.shape))
+        logposterior = None if logposterior is None else np.ascontiguousarray(logposterior, dtype='f8').reshape(self.nchains)
+        iterations = None if iterations is None else np.ascontiguousarray(iterations, dtype='i8').reshape(self.nchains)
+        self._check(self._lib.dl_nuts_set_state(self._handle, _f64_ptr(coords), _f64_ptr(logposterior), None if iterations is None else iterations.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                self._stream(stream)))
+
+    def get_state(self, stream=None):
+        """(points [nchains, P], log-posteriors, iteration counters, log step sizes) as numpy arrays; synchronises."""
+        coords, logp, logeps = np.empty((self.nchains, self.n_params)), np.empty(self.nchains), np.empty(self.nchains)
+        iterations = np.empty(self.nchains, dtype='i8')
+        self._check(self._lib.dl_nuts_get_state(self._handle, _f64_ptr(coords), _f64_ptr(logp), iterations.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _f64_ptr(logeps),
+                                                self._stream(stream)))
+        return coords, logp, iterations, logeps
+
+    def set_adaptation(self, enabled, target_acceptance=0.8, initial_step_size=1., stream=None):
+        self._check(self._lib.dl_nuts_set_adaptation(self._handle, int(bool(enabled)), float(target_acceptance), float(np.log(initial_step_size)), self._stream(stream)))
+
+    def buffers(self, quota):
+        """Record buffers of one batch: coords [nchains, quota, P], logposterior [nchains, quota], info [nchains, quota, 5], count [nchains] (zeroed)."""
+        import torch
+        device = torch.device('cuda', self.device)
+        return (torch.empty((self.nchains, quota, self.n_params), dtype=torch.float64, device=device), torch.empty((self.nchains, quota), dtype=torch.float64, device=device),
+                torch.empty((self.nchains, quota, 5), dtype=torch.float64, device=device), torch.zeros(self.nchains, dtype=torch.int32, device=device))
+
+    def run(self, nsteps, quota, buffers, thin_by=1, stream=None):
+        """Enqueue ``nsteps`` leapfrog steps of every chain into the record ``buffers`` of a batch of ``quota`` records per chain (asynchronous)."""
+        coords, logp, info, count = buffers
+        self._check(self._lib.dl_nuts_run(self._handle, int(nsteps), int(quota), int(thin_by), ctypes.c_void_p(coords.data_ptr()), ctypes.c_void_p(logp.data_ptr()),
+                                          ctypes.c_void_p(info.data_ptr()), ctypes.c_void_p(count.data_ptr()), self._stream(stream)))
+
+    def close(self):
+        if getattr(self, '_handle', None):
+            self._lib.dl_nuts_destroy(self._handle)
             self._handle = None
 
     def __del__(self):

@@ -1031,4 +1031,7 @@ def __getattr__(name):
     if name == 'HMCSampler':
         from . import hmc
         return hmc.HMCSampler
+    if name == 'NUTSSampler':
+        from . import nuts
+        return nuts.NUTSSampler
     raise AttributeError('module {!r} has no attribute {!r}'.format(__name__, name))

@@ -313,6 +313,44 @@ int  dl_mh_get_state(dl_mh* mh, double* coords, double* logposterior, int64_t* w
 /* integer properties: "nchains", "vectorize", "n_params", "tries", "cycle" (entries of the parameter cycler), "max_tries" */
 int64_t dl_mh_info(const dl_mh* mh, const char* key);
 
+/* ---- device-resident No-U-Turn sampler ------------------------------------------------------------------------------------------------------
+ * The reference's NUTSSampler (desilike/samplers/nuts.py: blackjax.nuts around jax.value_and_grad of one chain) as multinomial NUTS (csrc/dl_nuts.h states the
+ * algorithm and the random draws) on ``nchains`` chains resident on the GPU.  Chains are ASYNCHRONOUS: every step of dl_nuts_run advances every chain by one
+ * leapfrog step -- one gradient batch of the pending positions, then one kernel that processes the new leaf of every chain and, for a chain whose trajectory
+ * ends, records its sample, updates its dual averaging, draws a fresh momentum and makes the first drift of its next trajectory -- so no chain waits for the
+ * deepest tree.  Nothing in dl_nuts_run allocates or synchronises.  Errors: non-zero, message via dl_last_error(NULL). */
+typedef struct dl_nuts dl_nuts;
+/* chain_ids[nchains] global index of every chain (NULL: 0 .. nchains - 1; keys the draws: a chain is the same on any rank); max_num_doublings in [1, 15];
+ * divergence_threshold > 0 (a leaf with H - H0 above it, or H NaN, is divergent); offset: constant added to every log-posterior (posterior contexts marginalised
+ * once over linear parameters); gradient_mode 0 auto (dl_eval_logposterior_grad, central differences where it returns 2), 1 analytic (an error outside its scope),
+ * 2 finite; fd_delta[P, 2] (lower, upper step: Parameter.delta) and fd_limits[P, 2] (prior bounds the steps are shortened to) for central differences (host, may
+ * be NULL unless gradient_mode is 2).  The context has 1 .. 64 parameters. */
+int  dl_nuts_create(dl_nuts** out, dl_ctx* ctx, int32_t nchains, const int32_t* chain_ids, int32_t max_num_doublings, double divergence_threshold, uint64_t seed,
+                    double offset, int32_t gradient_mode, const double* fd_delta, const double* fd_limits);
+void dl_nuts_destroy(dl_nuts* nuts);
+/* inverse mass matrix (host): its diagonal [P] (dense = 0) or the symmetric positive-definite matrix [P, P] (dense = 1; the factor of M = inverse_mass^-1 the
+ * momenta are drawn with is computed here), and the step size of every chain (replaces the adapted ones); synchronises */
+int  dl_nuts_set_mass(dl_nuts* nuts, const double* inverse_mass, int32_t dense, double step_size, void* hip_stream);
+/* host arrays: coords[nchains, P] (finite), logposterior[nchains] (NULL: evaluated here with the gradient, which is evaluated in any case; must be finite),
+ * iteration_counters[nchains] (NULL: 0) -- the trajectory counter that keys each chain's draws (resume); every chain waits at a trajectory boundary; synchronises */
+int  dl_nuts_set_state(dl_nuts* nuts, const double* coords, const double* logposterior, const int64_t* iteration_counters, void* hip_stream);
+/* host arrays (any may be NULL): current points [nchains, P], their log-posteriors, iteration counters, and per chain the dual-averaged log step size
+ * (log eps-bar; the step size in use when adaptation is off); synchronises */
+int  dl_nuts_get_state(dl_nuts* nuts, double* coords, double* logposterior, int64_t* iteration_counters, double* log_step_size, void* hip_stream);
+/* enabled != 0: per-chain Nesterov dual averaging of the step size towards target_acceptance from every chain's next trajectory on, restarted at
+ * initial_log_step_size (mu = log(10 eps0), gamma 0.05, t0 10, kappa 0.75); enabled = 0: the step sizes stay as they are */
+int  dl_nuts_set_adaptation(dl_nuts* nuts, int32_t enabled, double target_acceptance, double initial_log_step_size, void* hip_stream);
+/* ``nsteps`` leapfrog steps of every chain, enqueued on ``hip_stream`` (asynchronous).  Every ``thin_by``-th trajectory of a chain (by its iteration counter) is
+ * recorded into slot out_count_dev[c] of out_coords_dev[nchains, quota, P], out_logp_dev[nchains, quota], out_info_dev[nchains, quota, 5] (tree depth, leapfrog
+ * steps, divergent flag -- 0, 1 energy error, 2 a leaf outside the support --, acceptance statistic, energy of the sample) and the count incremented; a chain whose count reached ``quota`` stops at its trajectory's
+ * end (its row is still evaluated and ignored).  The counts are NOT reset: the caller zeroes them at the start of a batch and calls dl_nuts_run with the same
+ * buffers until every count is ``quota`` (how the calls are chunked does not change the chains). */
+int  dl_nuts_run(dl_nuts* nuts, int64_t nsteps, int32_t quota, int32_t thin_by, double* out_coords_dev, double* out_logp_dev, double* out_info_dev,
+                 int32_t* out_count_dev, void* hip_stream);
+/* integer properties: "nchains", "n_params", "steps" (leapfrog steps enqueued so far), "max_num_doublings", "finite" (1 once central differences are in use),
+ * "dense", "adapt" */
+int64_t dl_nuts_info(const dl_nuts* nuts, const char* key);
+
 /* ---- MLP emulator training ---------------------------------------------------------------------------------------
  * The reference trains its MLP emulators through the third-party engine ``cosmoprimo.emulators.tools.MLPEmulatorEngine`` (desilike/emulators/__init__.py:510-533;
  * network structure: emulators/conversion.py:20-96).  Here: fp64 mini-batch Adam on the mean squared error of the (already scaled) outputs, entirely on the device

@@ -77,6 +77,12 @@ struct dl_ctx {
     double *grad_wtT = nullptr, *grad_zero = nullptr, *grad_delta = nullptr, *grad_y = nullptr, *grad_phys = nullptr;
     int32_t* grad_status = nullptr;
     int64_t grad_cap = 0;
+    // analytic gradient of an emulated observable (dl_emu_grad.h): transposed folded operator G^T [eg_ngt, 19 N_pad] (rows h < n_basis), U and V [cap, 19, N_pad],
+    // Q [cap, 1 + n_var, 19], dJ / d basis [cap, eg_ngt]
+    double *eg_gt = nullptr, *eg_u = nullptr, *eg_v = nullptr, *eg_q = nullptr, *eg_gb = nullptr;
+    double* eg_wt[3] = {nullptr, nullptr, nullptr};   // per MLP engine: its kernels transposed [out][in], packed (the backward pass)
+    int eg_ngt = 0;
+    int64_t eg_cap = 0;
     // the workspaces are shared by every call on this context: a call on another stream than the previous one waits for it (event recorded on the old stream
     // at the moment of the switch: calls that stay on one stream pay nothing)
     hipStream_t last_stream = nullptr;
@@ -480,6 +486,7 @@ void dl_destroy(dl_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     for (double* p : {ctx->grad_wtT, ctx->grad_zero, ctx->grad_delta, ctx->grad_y, ctx->grad_phys}) if (p) (void)hipFree(p);
+    for (double* p : {ctx->eg_gt, ctx->eg_u, ctx->eg_v, ctx->eg_q, ctx->eg_gb, ctx->eg_wt[0], ctx->eg_wt[1], ctx->eg_wt[2]}) if (p) (void)hipFree(p);
     if (ctx->grad_status) (void)hipFree(ctx->grad_status);
     void* ptrs[] = {ctx->arena_dev, ctx->priors_dev, ctx->wt_white_dev, ctx->wt_frag_dev, ctx->bias_white_dev, ctx->wt_full_dev, ctx->bias_full_dev, ctx->wh_dev,
                     ctx->bias_wh_dev, ctx->flatdata_dev, ctx->transform_dev, ctx->tconst_dev, ctx->power_ws, ctx->delta_ws, ctx->flat_ws, ctx->stencil_ws, ctx->theta_stage, ctx->out_stage,
@@ -779,11 +786,97 @@ int dl_eval_fisher(dl_ctx* ctx, const double* centers_dev, const double* steps_d
     return 0;
 }
 
+// Emulated observable (dl_emu_grad.h), per pass of at most 2048 points: theory records (basis, monomial rows) -> U = G . basis (MFMA) -> per point: rows, Gram matrix,
+// the solve of the evaluation path (log-posterior, status) and the adjoint V, Q -> dJ / d basis = V . G^T (tiled split-K GEMM) -> back through the MLP engines, the
+// monomials and the priors.
+static int dl_eval_logposterior_grad_emu(dl_ctx* ctx, const double* theta_dev, int64_t B, double* logposterior_dev, double* grad_dev, int32_t* status_dev, hipStream_t stream) {
+    const int64_t per_pass = 2048;
+    const int P = ctx->n_params, Np = ctx->N_pad;
+    const DlObsDev& o = ctx->obs_kernarg[0];
+    dl_prof_events.start = dl_prof_events.stop = nullptr;
+    const int64_t K = (int64_t)DL_FG_NM * Np;
+    if (!ctx->eg_gt) {
+        // G^T [h][(m, j)] = W~[j][(h, m)] (the operator gfrag holds in fragment order), rows up to a multiple of 128 (the N tile of the tiled GEMM) are zero
+        const int Kp = ctx->K_pad, ngt = (o.n_basis + 127) / 128 * 128;
+        std::vector<double> w((size_t)Np * Kp), gt((size_t)ngt * K, 0.);
+        DL_HIP_CHECK(ctx, hipMemcpy(w.data(), ctx->wt_white_dev, w.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int h = 0; h < o.n_basis; ++h)
+            for (int m = 0; m < DL_FG_NM; ++m)
+                for (int j = 0; j < Np; ++j) gt[(size_t)h * K + (size_t)m * Np + j] = w[(size_t)j * Kp + o.col_offset + (size_t)h * DL_N_MONO + m];
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->eg_gt, gt.size() * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMemcpy(ctx->eg_gt, gt.data(), gt.size() * sizeof(double), hipMemcpyHostToDevice));
+        ctx->eg_ngt = ngt;
+        for (int ie = 0; ie < 3; ++ie) {   // transposed kernels of the MLP engines
+            const DlObsDev::Engine& e = o.eng[ie];
+            if (e.type != 0) continue;
+            size_t n = 0, nt = 0;
+            for (int l = 0; l < e.n_layers; ++l) { n += (size_t)e.widths[l] * e.widths[l + 1] + e.widths[l + 1]; nt += (size_t)e.widths[l] * e.widths[l + 1]; }
+            std::vector<double> wh(n), wt(nt);
+            DL_HIP_CHECK(ctx, hipMemcpy(wh.data(), e.weights, n * sizeof(double), hipMemcpyDeviceToHost));
+            size_t off = 0, offt = 0;
+            for (int l = 0; l < e.n_layers; ++l) {
+                const int nin = e.widths[l], nout = e.widths[l + 1];
+                for (int i = 0; i < nin; ++i)
+                    for (int q = 0; q < nout; ++q) wt[offt + (size_t)q * nin + i] = wh[off + (size_t)i * nout + q];
+                off += (size_t)nin * nout + nout;
+                offt += (size_t)nin * nout;
+            }
+            DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->eg_wt[ie], nt * sizeof(double)));
+            DL_HIP_CHECK(ctx, hipMemcpy(ctx->eg_wt[ie], wt.data(), nt * sizeof(double), hipMemcpyHostToDevice));
+        }
+    }
+    const int64_t need = std::min<int64_t>(B, per_pass);
+    if (dl_reserve(ctx, need)) return 1;   // (the point records: feat_ws)
+    if (need > ctx->eg_cap || !ctx->grad_status) {
+        DL_HIP_CHECK(ctx, hipDeviceSynchronize());   // (kernels of earlier calls may still use the buffers about to be freed)
+        for (double** p : {&ctx->eg_u, &ctx->eg_v, &ctx->eg_q, &ctx->eg_gb}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+        if (ctx->grad_status) { (void)hipFree(ctx->grad_status); ctx->grad_status = nullptr; }
+        ctx->eg_cap = 0;
+        ctx->grad_cap = 0;
+        const int64_t cap = std::max<int64_t>((need + 63) / 64 * 64, 256);     // (whole 64-row tiles of the tiled GEMM)
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->eg_u, (size_t)cap * K * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->eg_v, (size_t)cap * K * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->eg_q, (size_t)cap * (1 + ctx->n_var) * DL_N_MONO * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->eg_gb, std::max<size_t>(2 * (size_t)cap, (size_t)cap + 16384 + 2048) * ctx->eg_ngt * sizeof(double)));   // (split-K slabs)
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->grad_status, (size_t)cap * sizeof(int32_t)));
+        DL_HIP_CHECK(ctx, hipMemset(ctx->eg_v, 0, (size_t)cap * K * sizeof(double)));      // (rows of the last GEMM tile beyond the batch are read: finite)
+        DL_HIP_CHECK(ctx, hipDeviceSynchronize());
+        ctx->eg_cap = cap;
+    }
+    for (int64_t b0 = 0; b0 < B; b0 += per_pass) {
+        const int64_t nb = std::min<int64_t>(per_pass, B - b0);
+        const double* th = theta_dev + (size_t)b0 * P;
+        int32_t* st = status_dev ? status_dev + b0 : ctx->grad_status;
+        dl_launch_fullshape(ctx->obs_kernarg.data(), 1, th, P, nb, ctx->power_ws, ctx->K_pad, nullptr, 0, stream, ctx->feat_ws, ctx->feat_ld, 0, nullptr);
+        dl_launch_emu_grad_u(ctx->feat_ws, ctx->feat_ld, o.feat_off, o.nb_pad, ctx->gfrag_dev[0], ctx->eg_u, Np, Np, nb, stream);
+        dl_launch_emu_grad_adjoint(ctx->feat_ws, ctx->feat_ld, o.feat_off, o.nb_pad, ctx->n_var, ctx->eg_u, Np, Np, ctx->bias_white_dev, ctx->marg, th, P, ctx->priors_dev,
+                                   logposterior_dev + b0, st, ctx->eg_v, ctx->eg_q, nb, stream);
+        // dJ / d basis = V [nb, 19 N_pad] . G^T, K = 19 N_pad split over the chip (one 64-row tile per 64 points and N = 128 alone are 32 workgroups at 2048
+        // points); the backward kernel sums the slabs
+        int cps = 0;
+        const int n_slabs = dl_gemm_tiled_splits(nb, ctx->eg_ngt, (int)K, &cps);
+        const int64_t slab_stride = nb * (int64_t)ctx->eg_ngt;
+        dl_launch_window_gemm_tiled(ctx->eg_v, K, ctx->eg_gt, K, ctx->eg_gb, slab_stride, ctx->eg_ngt, nb, ctx->eg_ngt, (int)K, n_slabs, cps, stream, 0);
+        dl_launch_emu_grad_backprop(o, th, P, ctx->priors_dev, ctx->eg_gb, ctx->eg_ngt, n_slabs, slab_stride, ctx->eg_q, st, ctx->eg_wt, grad_dev + (size_t)b0 * P, nb, stream);
+    }
+    DL_HIP_CHECK(ctx, hipGetLastError());
+    return 0;
+}
+
 // log-posterior and its gradient: theory -> residual rows d~ (direct GEMM) -> chi2 + priors, Y = -d~ W~ (second GEMM) -> gradient workgroups -> chain rule.
-// Returns 2 (nothing launched) when the context is outside the analytic gradient's scope (dl_fullshape_grad.h): the caller differentiates numerically.
+// Returns 2 (nothing launched) when the context is outside the analytic gradient's scope (dl_fullshape_grad.h, dl_emu_grad.h): the caller differentiates numerically.
 int dl_eval_logposterior_grad(dl_ctx* ctx, const double* theta_dev, int64_t B, double* logposterior_dev, double* grad_dev, int32_t* status_dev, void* hip_stream) {
     if (!ctx) { g_last_error = "dl_eval_logposterior_grad: null context"; return 1; }
     if (B < 0 || (B > 0 && (!theta_dev || !logposterior_dev || !grad_dev))) return dl_fail(ctx, "dl_eval_logposterior_grad: invalid argument");
+    // emulated: one observable on the feature path, MLP engines (dl_emu_grad.h)
+    const bool emu = ctx->feat_ok && !ctx->any_transform && !ctx->priors_general && ctx->n_obs == 1 && !ctx->any_stacked &&
+                     dl_emu_grad_applicable(ctx->obs_kernarg[0], ctx->N_pad, ctx->n_solved);
+    if (emu) {
+        if (B == 0) return 0;
+        DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+        if (dl_order_streams(ctx, (hipStream_t)hip_stream)) return 1;
+        return dl_eval_logposterior_grad_emu(ctx, theta_dev, B, logposterior_dev, grad_dev, status_dev, (hipStream_t)hip_stream);
+    }
     if (ctx->feat_ok || ctx->any_transform || ctx->n_solved != 0 || ctx->priors_general || !dl_grad_applicable(ctx->obs_kernarg.data(), ctx->n_obs)) return 2;
     if (B == 0) return 0;
     hipStream_t stream = (hipStream_t)hip_stream;

@@ -142,5 +142,14 @@ bool dl_launch_fullshape_ens(const DlObsDev* obs_host, int n_obs, const DlObsDev
 bool dl_grad_applicable(const DlObsDev* obs_host, int n_obs);
 void dl_launch_fullshape_grad(const DlObsDev* obs_host, int n_obs, const DlObsDev* obs_dev, const double* theta, int n_params, int64_t B, const double* Y, int64_t ldy, double* gphys,
                               const double* priors, const int32_t* status, double* grad, hipStream_t stream);
+// analytic gradient of one emulated observable on the feature path (dl_emu_grad.h)
+bool dl_emu_grad_applicable(const DlObsDev& obs, int N_pad, int n_solved);
+void dl_launch_emu_grad_u(const double* feat, int64_t feat_ld, int64_t feat_off, int nb_pad, const double* gfrag, double* U, int64_t ldu, int N_pad, int64_t B, hipStream_t stream);
+void dl_launch_emu_grad_adjoint(const double* feat, int64_t feat_ld, int64_t feat_off, int nb_pad, int n_var, const double* U, int64_t ldu, int N_pad, const double* bias,
+                                const DlMargDev& mg, const double* theta, int n_params, const double* priors, double* logpost, int32_t* status, double* V, double* Q,
+                                int64_t B, hipStream_t stream);
+void dl_launch_emu_grad_backprop(const DlObsDev& obs, const double* theta, int n_params, const double* priors, const double* gb, int64_t ldg, int n_slabs, int64_t slab_stride,
+                                 const double* Q, const int32_t* status, const double* const* wT /* [3]: transposed MLP kernels per engine */, double* grad, int64_t B,
+                                 hipStream_t stream);
 // last-error string of the C ABI (thread-local, read by dl_last_error(NULL)); set by translation units other than dl_api.hip
 void dl_set_last_error(const char* msg);

@@ -1804,3 +1804,57 @@ void dl_launch_finalize_marg(const double* dtilde, int64_t ld, int n, int rows_p
         }
     }
 }
+
+// ---- analytic gradient of an emulated observable (dl_emu_grad.h) ------------------------------------------------------------------------------------------------
+#include "dl_emu_grad.h"
+
+static size_t dl_eg_adjoint_shared_bytes(int n_var, int n_s, int N_pad) {
+    const int nr = 1 + n_s;
+    return ((size_t)(1 + n_var) * DL_FG_MONO_LD + 2 * (size_t)nr * N_pad + (size_t)nr * nr + n_s + (size_t)n_s * n_s) * sizeof(double);
+}
+
+bool dl_emu_grad_applicable(const DlObsDev& o, int N_pad, int n_solved) {
+    if (o.theory != 3 || o.n_pass != 0 || o.n_mono != DL_N_MONO || o.eng[0].type != 0) return false;
+    for (int ie = 1; ie < 3; ++ie) if (o.eng[ie].type != 0 && o.eng[ie].type != -1) return false;
+    if (o.n_basis != o.eng[0].widths[o.eng[0].n_layers] + 1 || o.n_x > DL_MAX_X) return false;
+    if (N_pad % 128 != 0 || n_solved > DL_EG_MAX_SOLVED) return false;
+    if (dl_eg_adjoint_shared_bytes(o.n_var, n_solved, N_pad) > 64 * 1024 || dl_eg_backprop_doubles(o) * sizeof(double) > 64 * 1024) return false;
+    return (size_t)DL_FG_PTS * dl_fg_lds_stride(o.nb_pad) * sizeof(double) <= 64 * 1024;
+}
+
+void dl_launch_emu_grad_u(const double* feat, int64_t feat_ld, int64_t feat_off, int nb_pad, const double* gfrag, double* U, int64_t ldu, int N_pad, int64_t B, hipStream_t stream) {
+    const size_t shm = (size_t)DL_FG_PTS * dl_fg_lds_stride(nb_pad) * sizeof(double);
+    if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)dl_emu_grad_u_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    DL_LAUNCH(dl_emu_grad_u_kernel, dim3((unsigned)((B + DL_FG_PTS - 1) / DL_FG_PTS), (unsigned)(N_pad / 32)), dim3(128), shm, stream, feat, feat_ld, feat_off, nb_pad, gfrag,
+              U, ldu, B);
+}
+
+void dl_launch_emu_grad_adjoint(const double* feat, int64_t feat_ld, int64_t feat_off, int nb_pad, int n_var, const double* U, int64_t ldu, int N_pad, const double* bias,
+                                const DlMargDev& mg, const double* theta, int n_params, const double* priors, double* logpost, int32_t* status, double* V, double* Q,
+                                int64_t B, hipStream_t stream) {
+    const size_t shm = dl_eg_adjoint_shared_bytes(n_var, mg.n_s, N_pad);
+    auto launch = [&](auto kernel) {
+        if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        DL_LAUNCH(kernel, dim3((unsigned)B), dim3(64), shm, stream, feat, feat_ld, feat_off, nb_pad, n_var, U, ldu, N_pad, bias, mg, theta, n_params, priors, logpost, status,
+                  V, Q, B);
+    };
+    switch (mg.n_s) {   // (dl_emu_grad_applicable: at most DL_EG_MAX_SOLVED)
+        case 0: launch(dl_emu_grad_adjoint_kernel<0>); break;
+        case 1: launch(dl_emu_grad_adjoint_kernel<1>); break;
+        case 2: launch(dl_emu_grad_adjoint_kernel<2>); break;
+        case 3: launch(dl_emu_grad_adjoint_kernel<3>); break;
+        case 4: launch(dl_emu_grad_adjoint_kernel<4>); break;
+        case 5: launch(dl_emu_grad_adjoint_kernel<5>); break;
+        case 6: launch(dl_emu_grad_adjoint_kernel<6>); break;
+        case 7: launch(dl_emu_grad_adjoint_kernel<7>); break;
+        default: launch(dl_emu_grad_adjoint_kernel<8>); break;
+    }
+}
+
+void dl_launch_emu_grad_backprop(const DlObsDev& obs, const double* theta, int n_params, const double* priors, const double* gb, int64_t ldg, int n_slabs, int64_t slab_stride, const double* Q,
+                                 const int32_t* status, const double* const* wT, double* grad, int64_t B, hipStream_t stream) {
+    const size_t shm = dl_eg_backprop_doubles(obs) * sizeof(double);
+    if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)dl_emu_grad_backprop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    const DlEgWT w = {{wT[0], wT[1], wT[2]}};
+    DL_LAUNCH(dl_emu_grad_backprop_kernel, dim3((unsigned)B), dim3(64), shm, stream, obs, theta, n_params, priors, gb, ldg, n_slabs, slab_stride, Q, status, w, grad, B);
+}

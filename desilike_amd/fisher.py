@@ -144,7 +144,8 @@ def logposterior_value_and_grad(likelihood, theta, method='auto'):
     r"""Log-posterior and its gradient w.r.t. the varied parameters for a batch of points.
 
     ``method='analytic'``: ``dl_eval_logposterior_grad`` -- the gradient is formed on the device from the theory's own derivatives (csrc/dl_fullshape_grad.h:
-    one forward pass, one extra GEMM, one gradient pass: about 2.5 evaluations instead of 2 P + 1), for Kaiser full-shape likelihoods with uniform / Gaussian priors;
+    one forward pass, one extra GEMM, one gradient pass: about 2.5 evaluations instead of 2 P + 1), for Kaiser full-shape likelihoods with uniform / Gaussian priors,
+    and one MLP-emulated velocileptors observable with solved parameters (csrc/dl_emu_grad.h);
     ``'finite'``: central differences evaluated as ONE GPU batch (below); ``'auto'``: analytic where the context supports it, else central differences.
 
     What gradient-based samplers ask of the likelihood (``jax.value_and_grad(logposterior)``: desilike/samplers/hmc.py:194, nuts.py:205, mclmc.py); the reference
@@ -162,12 +163,12 @@ def logposterior_value_and_grad(likelihood, theta, method='auto'):
     if method != 'finite':
         ctx = likelihood._get_context()
         th = torch.as_tensor(theta, dtype=torch.float64, device=torch.device('cuda', ctx.device)).contiguous()
-        out = ctx.eval_logposterior_grad(th) if not len(likelihood.solved_params) else None
+        out = ctx.eval_logposterior_grad(th)   # (None: outside the analytic gradient's scope, the context decides)
         if out is not None:
             return out[0].cpu().numpy(), out[1].cpu().numpy()
         if method == 'analytic':
             raise NotImplementedError('the analytic gradient covers Kaiser full-shape likelihoods (uniform template knots, no counter terms, no damping, no transform, no solved '
-                                      'parameters, uniform / norm priors): use method="finite"')
+                                      'parameters) and one MLP-emulated velocileptors observable (solved parameters allowed), with uniform / norm priors: use method="finite"')
     lower, upper = np.empty((B, P)), np.empty((B, P))
     for ip, param in enumerate(varied):
         _, lo, hi = param.delta

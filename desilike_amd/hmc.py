@@ -79,8 +79,8 @@ class HMCSampler(BasePosteriorSampler):
         import torch
         P = q.shape[1]
         out = None
-        if q.is_cuda and self.gradient != 'finite' and not len(getattr(self.likelihood, 'solved_params', [])):
-            out = self.likelihood._get_context().eval_logposterior_grad(q.contiguous())
+        if q.is_cuda and self.gradient != 'finite':
+            out = self.likelihood._get_context().eval_logposterior_grad(q.contiguous())   # (None: outside the analytic gradient's scope, the context decides)
             if out is None and self.gradient == 'analytic': raise NotImplementedError('this likelihood is outside the analytic gradient: use gradient="finite"')
         if out is None:
             # central differences, ONE batch of C (2 P + 1) rows (steps: Parameter.delta, shortened where a prior bound is closer)

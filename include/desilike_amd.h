@@ -176,8 +176,11 @@ int  dl_eval_fisher(dl_ctx* ctx, const double* centers_dev, const double* steps_
  * samplers/nuts.py:205): d logL / d theta = Y . d(theory vector) / d theta with Y = -W~^T d~, the derivative contracted on the fly by the theory's gradient kernel
  * (qpar / qper through every AP mode, df, dm, dn, b1 of either tracer, sn0; the spline of the template is linear in its data, so d / d dm is the spline of
  * d template / d dm), + the gradient of uniform / Gaussian priors.  Rows whose log-posterior is -inf get a zero gradient.  status_dev may be NULL.
- * Returns 0; 1 on error; 2 -- nothing launched -- when the context is outside the scope (Kaiser tracers without counter terms on uniform template knots, no damping,
- * no observable transform, no solved parameters, uniform / norm priors): differentiate numerically then (dl_eval_logposterior on a stencil). */
+ * Returns 0; 1 on error; 2 -- nothing launched -- when the context is outside the scope: differentiate numerically then (dl_eval_logposterior on a stencil).  The scope:
+ * uniform / norm priors, no observable transform, and either Kaiser tracers without counter terms on uniform template knots, no damping, no solved parameters
+ * (dl_fullshape_grad.h), or ONE emulated velocileptors observable on the feature path whose table, sigma8 and fsigma8 engines are MLPs (or constants), with up to 8
+ * '.marg' / '.best' solved parameters (dl_emu_grad.h; the log-posterior equals dl_eval_logposterior's to rounding).  Taylor engines, the stacked table layout and
+ * several emulated observables return 2. */
 int  dl_eval_logposterior_grad(dl_ctx* ctx, const double* theta_dev, int64_t B, double* logposterior_dev, double* grad_dev, int32_t* status_dev, void* hip_stream);
 
 /* Theory state of observable ``iobs`` for parity / plots / emulation:

@@ -30,6 +30,7 @@ SYMBOLS = {
     'dl_eval_logposterior': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_logposterior_grad': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_fisher': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_eval_fisher_analytic': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_theory': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_batch_host': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_int32_p, _c_double_p]),
     'dl_eval_tns_tables': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
@@ -417,6 +418,29 @@ class Context(object):
         self._check(self._lib.dl_eval_fisher(self._handle, ctypes.c_void_p(centers.data_ptr()), ctypes.c_void_p(steps.data_ptr()), B, ctypes.c_void_p(hessian.data_ptr()),
                                              ctypes.c_void_p(gradient.data_ptr()), ctypes.c_void_p(offset.data_ptr()), ctypes.c_void_p(stream)))
         return hessian, gradient, offset
+
+    def eval_fisher_analytic(self, centers, hessian=None, gradient=None, offset=None, stream=None):
+        """The Fisher algebra from exact derivative rows (``dl_eval_fisher_analytic``; csrc/dl_fullshape_jac.h): ``centers [B, P]`` -> ``(hessian [B, P, P],
+        gradient [B, P], offset [B])`` (float64 device tensors, allocated if ``None``; ``False``: that output is not wanted -- a NULL pointer -- and comes back as
+        ``None``); asynchronous on ``stream``.  Returns ``None`` when the context is outside the Jacobian kernel's scope (the caller uses :meth:`eval_fisher`)."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(centers.device).cuda_stream
+        B, P = centers.shape
+        if self.expand is not None:
+            raise NotImplementedError('Fisher algebra with parameters derived by an expression: differentiate w.r.t. the device columns and apply the chain rule on the host')
+        assert P == self.n_params and centers.is_contiguous() and centers.dtype == torch.float64
+        outputs = []
+        for tensor, shape in [(hessian, (B, P, P)), (gradient, (B, P)), (offset, (B,))]:
+            if tensor is None: tensor = torch.empty(shape, dtype=torch.float64, device=centers.device)
+            if tensor is False: tensor = None
+            else: assert tensor.is_contiguous() and tensor.dtype == torch.float64 and tuple(tensor.shape) == shape
+            outputs.append(tensor)
+        rc = self._lib.dl_eval_fisher_analytic(self._handle, ctypes.c_void_p(centers.data_ptr()), B, *[None if tensor is None else ctypes.c_void_p(tensor.data_ptr()) for tensor in outputs],
+                                               ctypes.c_void_p(stream))
+        if rc == 2: return None
+        self._check(rc)
+        return tuple(outputs)
 
     def profile_enable(self, every=1, only=None):
         """Attach HIP events to the kernels' dispatch packets on one ``eval_batch`` call out of ``every`` (0 / False: off); ``only``: 'theory' /

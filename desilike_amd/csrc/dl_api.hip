@@ -77,6 +77,9 @@ struct dl_ctx {
     double *grad_wtT = nullptr, *grad_zero = nullptr, *grad_delta = nullptr, *grad_y = nullptr, *grad_phys = nullptr;
     int32_t* grad_status = nullptr;
     int64_t grad_cap = 0;
+    // analytic Fisher (dl_eval_fisher_analytic): residual rows d~ [cap, N_pad], Jacobian rows [cap P (whole 64-row GEMM tiles), K_pad], their window product (split-K slabs)
+    double *fa_resid = nullptr, *fa_jac = nullptr, *fa_rows = nullptr;
+    int64_t fa_cap = 0, fa_slab_rows = 0;
     // analytic gradient of an emulated observable (dl_emu_grad.h): transposed folded operator G^T [eg_ngt, 19 N_pad] (rows h < n_basis), U and V [cap, 19, N_pad],
     // Q [cap, 1 + n_var, 19], dJ / d basis [cap, eg_ngt]
     double *eg_gt = nullptr, *eg_u = nullptr, *eg_v = nullptr, *eg_q = nullptr, *eg_gb = nullptr;
@@ -486,6 +489,7 @@ void dl_destroy(dl_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     for (double* p : {ctx->grad_wtT, ctx->grad_zero, ctx->grad_delta, ctx->grad_y, ctx->grad_phys}) if (p) (void)hipFree(p);
+    for (double* p : {ctx->fa_resid, ctx->fa_jac, ctx->fa_rows}) if (p) (void)hipFree(p);
     for (double* p : {ctx->eg_gt, ctx->eg_u, ctx->eg_v, ctx->eg_q, ctx->eg_gb, ctx->eg_wt[0], ctx->eg_wt[1], ctx->eg_wt[2]}) if (p) (void)hipFree(p);
     if (ctx->grad_status) (void)hipFree(ctx->grad_status);
     void* ptrs[] = {ctx->arena_dev, ctx->priors_dev, ctx->wt_white_dev, ctx->wt_frag_dev, ctx->bias_white_dev, ctx->wt_full_dev, ctx->bias_full_dev, ctx->wh_dev,
@@ -781,6 +785,63 @@ int dl_eval_fisher(dl_ctx* ctx, const double* centers_dev, const double* steps_d
         }
         dl_launch_fisher(ctx->delta_ws, ctx->N_pad, ctx->n_white, n_slabs, slab_stride, bias, steps, P, nc, hessian_dev ? hessian_dev + (size_t)b0 * P * P : nullptr,
                          gradient_dev ? gradient_dev + (size_t)b0 * P : nullptr, offset_dev ? offset_dev + b0 : nullptr, stream);
+    }
+    DL_HIP_CHECK(ctx, hipGetLastError());
+    return 0;
+}
+
+// Fisher algebra from EXACT derivative rows (dl_fullshape_jac.h).  Per pass: theory -> chi2 GEMM with the residual output (d~; its partial chi2 are not used) -> Jacobian
+// kernel (pass x P rows) -> tiled window GEMM of those rows against W~ (no bias: the derivative of the residual) -> Gram kernel on [d~; D~_1 .. D~_P].
+// Returns 2 (nothing launched) outside the scope of the Jacobian kernel.
+int dl_eval_fisher_analytic(dl_ctx* ctx, const double* centers_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, void* hip_stream) {
+    if (!ctx) { g_last_error = "dl_eval_fisher_analytic: null context"; return 1; }
+    if (B < 0 || (B > 0 && !centers_dev)) return dl_fail(ctx, "dl_eval_fisher_analytic: invalid argument");
+    const int P = ctx->n_params, Np = ctx->N_pad, Kp = ctx->K_pad;
+    if (ctx->feat_ok || ctx->any_transform || ctx->n_solved != 0 || P > 31 || !dl_grad_applicable(ctx->obs_kernarg.data(), ctx->n_obs) ||
+        dl_fisher_waves(ctx->n_white, P, nullptr, nullptr) < 1) return 2;
+    if (B == 0) return 0;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    dl_prof_events.start = dl_prof_events.stop = nullptr;
+    DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (dl_order_streams(ctx, stream)) return 1;
+    // centres per pass: pass x (1 + P) x max(K_pad, N_pad) <= 16 Mi doubles -- at most 128 MiB of Jacobian rows, and large enough that 1024 centres of the benchmark
+    // shape (P = 6, K_pad = 1280) are one pass, whose launches fill the chip --, at most 2048 (the row range of the chi2 GEMM), in whole 64-row tiles
+    const int64_t per_pass = std::max<int64_t>(64, std::min<int64_t>(2048, ((int64_t)16 << 20) / ((int64_t)(1 + P) * std::max(Kp, Np))) / 64 * 64);
+    const int64_t need = std::min<int64_t>(B, per_pass);
+    if (dl_reserve(ctx, need)) return 1;
+    if (need > ctx->fa_cap) {
+        if (ctx->fa_cap > 0) DL_HIP_CHECK(ctx, hipDeviceSynchronize());   // (kernels of earlier calls may still use the buffers about to be freed)
+        for (double** p : {&ctx->fa_resid, &ctx->fa_jac, &ctx->fa_rows}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+        ctx->fa_cap = 0;
+        const int64_t cap = std::min<int64_t>(std::max<int64_t>((need + 63) / 64 * 64, 256), per_pass);
+        const size_t rows = ((size_t)cap * P + 63) / 64 * 64, slab_rows = std::max<size_t>(2 * rows, rows + 16384 + 2048);   // (split-K slabs under the present policy of dl_gemm_tiled_splits; every pass checks its own need against this)
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->fa_resid, (size_t)cap * Np * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->fa_jac, rows * Kp * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->fa_rows, slab_rows * Np * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMemset(ctx->fa_jac, 0, rows * Kp * sizeof(double)));      // (defined contents for the first use; the GEMM clamps its row reads to the batch and writes no row beyond it, so rows left by an earlier, larger call do not matter)
+        DL_HIP_CHECK(ctx, hipDeviceSynchronize());
+        ctx->fa_cap = cap;
+        ctx->fa_slab_rows = (int64_t)slab_rows;
+    }
+    const int xcd_local = dl_options().xcd_local;
+    for (int64_t b0 = 0; b0 < B; b0 += per_pass) {   // (no launch before every pass is known to fit the slab buffer: a retuned split policy is an error here, not an overflow)
+        int cps = 0;
+        const int64_t nr = std::min<int64_t>(per_pass, B - b0) * P;
+        if ((int64_t)dl_gemm_tiled_splits(nr, Np, Kp, &cps) * nr > ctx->fa_slab_rows) return dl_fail(ctx, "dl_eval_fisher_analytic: the split-K slabs of the window product exceed their buffer");
+    }
+    for (int64_t b0 = 0; b0 < B; b0 += per_pass) {
+        const int64_t nc = std::min<int64_t>(per_pass, B - b0), nr = nc * P;
+        const double* th = centers_dev + (size_t)b0 * P;
+        dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, th, P, nc, ctx->power_ws, Kp, nullptr, 0, stream, nullptr, 0, xcd_local ? dl_chi2_gemm_row_tile(nc, Np) : 0, ctx->obs_array_dev);
+        dl_launch_chi2_gemm(ctx->power_ws, Kp, ctx->wt_white_dev, Kp, ctx->bias_white_dev, ctx->delta_ws, nc, Np, Kp, nullptr, th, P, ctx->priors_dev, nullptr, nullptr, nullptr, 1, stream,
+                            ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data(), ctx->K_live, ctx->fa_resid, Np, ctx->wt_frag_dev);
+        dl_launch_fullshape_jac(ctx->obs_kernarg.data(), ctx->n_obs, ctx->obs_array_dev, th, P, nc, ctx->K_live, Kp, ctx->fa_jac, Kp, stream);
+        int cps = 0;
+        const int n_slabs = dl_gemm_tiled_splits(nr, Np, Kp, &cps);
+        const int64_t slab_stride = nr * (int64_t)Np;
+        dl_launch_window_gemm_tiled(ctx->fa_jac, Kp, ctx->wt_white_dev, Kp, ctx->fa_rows, slab_stride, Np, nr, Np, Kp, n_slabs, cps, stream, ctx->n_white);
+        dl_launch_fisher_rows(ctx->fa_resid, Np, ctx->fa_rows, Np, ctx->n_white, n_slabs, slab_stride, P, nc, hessian_dev ? hessian_dev + (size_t)b0 * P * P : nullptr,
+                              gradient_dev ? gradient_dev + (size_t)b0 * P : nullptr, offset_dev ? offset_dev + b0 : nullptr, stream);
     }
     DL_HIP_CHECK(ctx, hipGetLastError());
     return 0;

@@ -35,10 +35,12 @@ void dl_launch_fisher_stencil(const double* centers, const double* steps, int P,
 }
 
 // TILES = ceil((P + 1) / 16): 16 x 16 tiles of the Gram matrix per side (1 or 2).  One wavefront per centre, WAVES of them per workgroup.
-template <int TILES>
+// GIVEN: the rows already ARE derivatives (dl_eval_fisher_analytic): row (b, p) of `rows` = D~_p of centre b (the slabs of the window GEMM of the Jacobian rows, no bias),
+// d~ = row b of `resid` (bias included); nothing is differenced and `steps` / `bias` are not read.
+template <int TILES, bool GIVEN = false>
 __global__ __launch_bounds__(256) void dl_fisher_kernel(const double* __restrict__ rows, int64_t ld, int n, int n_slabs, int64_t slab_stride, const double* __restrict__ bias,
                                                         const double* __restrict__ steps, int P, int64_t B, int waves, int chunk, double* __restrict__ hessian,
-                                                        double* __restrict__ gradient, double* __restrict__ offset) {
+                                                        double* __restrict__ gradient, double* __restrict__ offset, const double* __restrict__ resid = nullptr, int64_t ldr = 0) {
     extern __shared__ __attribute__((aligned(16))) double dl_fi_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t b = (int64_t)blockIdx.x * waves + wave;
@@ -47,7 +49,7 @@ __global__ __launch_bounds__(256) void dl_fisher_kernel(const double* __restrict
     // the rows are staged `chunk` columns at a time (a multiple of 4; the whole row when it fits: short data vectors), the Gram tiles accumulate over the chunks
     const int n4 = 4 * ((n + 3) / 4), stride = chunk + 4;   // (+4 doubles: rows of an operand read 16 apart fall on different LDS banks)
     double* X = dl_fi_lds + (size_t)wave * (TILES * 16) * stride;
-    const double* row0 = rows + (size_t)b * S * ld;
+    const double* row0 = rows + (size_t)b * (GIVEN ? P : S) * ld;
     const int xr = lane & 15, g = lane >> 4;
     dl_fi_double4 acc[TILES][TILES];
 #pragma unroll
@@ -61,7 +63,13 @@ __global__ __launch_bounds__(256) void dl_fisher_kernel(const double* __restrict
         const int c0 = base + cc;
         for (int r = 0; r < TILES * 16; ++r) {
             dl_fi_double2 v = {0., 0.};
-            if (r == 0) {
+            if (GIVEN) {
+                if (r == 0) v = *reinterpret_cast<const dl_fi_double2*>(resid + (size_t)b * ldr + c0);
+                else if (r < nrows) {
+                    const double* dr = row0 + (size_t)(r - 1) * ld;
+                    for (int sl = 0; sl < n_slabs; ++sl) v += *reinterpret_cast<const dl_fi_double2*>(dr + (size_t)sl * slab_stride + c0);
+                }
+            } else if (r == 0) {
                 if (bias) v = *reinterpret_cast<const dl_fi_double2*>(bias + c0);
                 for (int sl = 0; sl < n_slabs; ++sl) v += *reinterpret_cast<const dl_fi_double2*>(row0 + (size_t)sl * slab_stride + c0);
             } else if (r < nrows) {
@@ -140,8 +148,23 @@ void dl_launch_fisher(const double* rows, int64_t ld, int n, int n_slabs, int64_
     const unsigned grid = (unsigned)((B + waves - 1) / waves);
     auto launch = [&](auto kernel) {
         if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        DL_LAUNCH(kernel, dim3(grid), dim3(64 * waves), shm, stream, rows, ld, n, n_slabs, slab_stride, bias, steps, P, B, waves, chunk, hessian, gradient, offset);
+        DL_LAUNCH(kernel, dim3(grid), dim3(64 * waves), shm, stream, rows, ld, n, n_slabs, slab_stride, bias, steps, P, B, waves, chunk, hessian, gradient, offset, (const double*)nullptr, (int64_t)0);
     };
     if (P + 1 <= 16) launch(dl_fisher_kernel<1>);
     else launch(dl_fisher_kernel<2>);
+}
+
+void dl_launch_fisher_rows(const double* resid, int64_t ldr, const double* drows, int64_t ld, int n, int n_slabs, int64_t slab_stride, int P, int64_t B, double* hessian,
+                           double* gradient, double* offset, hipStream_t stream) {
+    size_t shm = 0;
+    int chunk = 0;
+    const int waves = dl_fisher_waves(n, P, &shm, &chunk);
+    const unsigned grid = (unsigned)((B + waves - 1) / waves);
+    const double* const none = nullptr;
+    auto launch = [&](auto kernel) {
+        if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        DL_LAUNCH(kernel, dim3(grid), dim3(64 * waves), shm, stream, drows, ld, n, n_slabs, slab_stride, none, none, P, B, waves, chunk, hessian, gradient, offset, resid, ldr);
+    };
+    if (P + 1 <= 16) launch(dl_fisher_kernel<1, true>);
+    else launch(dl_fisher_kernel<2, true>);
 }

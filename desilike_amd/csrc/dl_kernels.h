@@ -142,6 +142,14 @@ bool dl_launch_fullshape_ens(const DlObsDev* obs_host, int n_obs, const DlObsDev
 bool dl_grad_applicable(const DlObsDev* obs_host, int n_obs);
 void dl_launch_fullshape_grad(const DlObsDev* obs_host, int n_obs, const DlObsDev* obs_dev, const double* theta, int n_params, int64_t B, const double* Y, int64_t ldy, double* gphys,
                               const double* priors, const int32_t* status, double* grad, hipStream_t stream);
+// analytic Jacobian (dl_fullshape_jac.h; scope: dl_grad_applicable): jac [B * P, ldj] = the rows d(theory vector) / d theta_p of every point, P rows per point, columns
+// [0, k_pad) of every row written (each observable its block at col_offset, the padding [k_live, k_pad) zeroed)
+void dl_launch_fullshape_jac(const DlObsDev* obs_host, int n_obs, const DlObsDev* obs_dev, const double* theta, int n_params, int64_t B, int k_live, int k_pad, double* jac, int64_t ldj,
+                             hipStream_t stream);
+// Fisher algebra on GIVEN derivative rows (dl_fisher.hip): X = [d~; D~_1 .. D~_P] with d~ = resid [B, ldr] (bias included) and D~_p = the sum of the n_slabs slabs of
+// drows [B * P, ld] (no bias); the Gram tiles and outputs of dl_launch_fisher
+void dl_launch_fisher_rows(const double* resid, int64_t ldr, const double* drows, int64_t ld, int n, int n_slabs, int64_t slab_stride, int P, int64_t B, double* hessian,
+                           double* gradient, double* offset, hipStream_t stream);
 // analytic gradient of one emulated observable on the feature path (dl_emu_grad.h)
 bool dl_emu_grad_applicable(const DlObsDev& obs, int N_pad, int n_solved);
 void dl_launch_emu_grad_u(const double* feat, int64_t feat_ld, int64_t feat_off, int nb_pad, const double* gfrag, double* U, int64_t ldu, int N_pad, int64_t B, hipStream_t stream);

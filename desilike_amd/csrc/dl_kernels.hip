@@ -26,6 +26,7 @@
 #include "dl_scalar_prefetch.h"
 #include "dl_ens_fold.h"
 #include "dl_fullshape_grad.h"
+#include "dl_fullshape_jac.h"
 
 thread_local DlProfEvents dl_prof_events;
 
@@ -492,6 +493,74 @@ void dl_launch_fullshape_grad(const DlObsDev* obs_host, int n_obs, const DlObsDe
     };
     if (nl3) launch(dl_fullshape_grad_kernel<3>); else launch(dl_fullshape_grad_kernel<5>);
     hipLaunchKernelGGL(dl_grad_finalize_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, obs_dev, n_obs, theta, n_params, priors, gphys, status, B, grad);
+}
+
+// ---- analytic Jacobian (dl_fullshape_jac.h): one workgroup per (point, observable) writes its column block of the P rows d(theory vector) / d theta_p ------------------
+// The gradient kernel's phases with the contraction replaced by per-element sums: the chain matrix beside the per-mu chain on wave 3, then per spline (template,
+// d template / d dm, d template / d dn) the sums over the mu nodes of the thread's own wavenumbers.  The gradient kernel's LDS (36 KB at the benchmark shape: four
+// workgroups per CU); 30 fp64 accumulators in pass 0 (NL = 3, two wavenumbers per thread) -- the register count and the absence of scratch are in DESIGN.md 6d.
+template <int NL, int KPT>
+__global__ __launch_bounds__(DL_FS_THREADS, 4) void dl_fullshape_jac_kernel(const DlObsDev* __restrict__ obs, const double* __restrict__ theta, int n_params, int k_live, int k_pad,
+                                                                             double* __restrict__ jac, int64_t ldj) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const DlObsDev& o = obs[blockIdx.y];
+    const int b = blockIdx.x, tid = threadIdx.x, nthr = DL_FS_THREADS;
+    constexpr int KT = DL_FS_KT;
+    const double* th = theta + (size_t)b * n_params;
+    const bool toep = o.toeplitz && !o.fixed_spline;
+    const DlFsShared s = dl_fs_shared_carve(lds, o.n_t, o.n_in, dl_fs_n_dd0(o), toep);
+    double* gw = s.pt + DL_PT_SIZE_FAST;
+    double* C = gw + (size_t)DL_MAX_MU * DL_GW;
+    double* Jpoint = jac + (size_t)b * n_params * ldj;
+    auto build = [&]() {
+        if (tid < KT) dl_fs_phase2_fir(tid, KT, o, s);
+        __syncthreads();
+        if (tid < KT) {
+            double dlt_pref[DL_TOEP_PREF];
+#pragma unroll
+            for (int it = 0; it < DL_TOEP_PREF; ++it) dlt_pref[it] = (tid + it * KT < o.n_t - 1) ? o.dlt[tid + it * KT] : 0.;
+            dl_fs_phase2d_toep(tid, KT, o, s, dlt_pref);
+        }
+        __syncthreads();
+    };
+    if (tid >= KT) {
+        const int m = tid - KT;
+        const bool mu_lane = m < o.n_mu;
+        DlMuCarry c;
+        dl_fs_mu_partA(o, th, mu_lane ? m : 0, c);
+        dl_fs_mu_partB(c);
+        if (mu_lane) { dl_fs_mu_partC(o, s, m, c, false); dl_fs_grad_weights(o, m, c, gw); }
+        if (tid == nthr - 1) { dl_fs_scalars(o, th, s, c, false); dl_fs_grad_weights_pad(o, gw); }
+        dl_fs_jac_chain_matrix(m, o, th, n_params, C);
+    } else dl_fs_knots(tid, KT, o, th, s);
+    if (blockIdx.y == gridDim.y - 1) dl_fs_jac_zero_tail(tid, nthr, n_params, k_live, k_pad, Jpoint, ldj);
+    __syncthreads();
+    if (toep) build();
+    double* J = Jpoint + o.col_offset;
+    dl_fs_jac_phase3<NL, KPT>(tid, nthr, o, s, gw, C, n_params, 0, J, ldj);
+    if (toep && o.templ == 1) {
+        for (int which = 0; which < 2; ++which) {
+            if (which == 0 ? o.dm.col < 0 : o.dn.col < 0) continue;
+            __syncthreads();                          // (everyone is done with the previous spline)
+            if (tid < KT) dl_fs_grad_knots(tid, KT, o, th, s, which);
+            __syncthreads();
+            build();
+            dl_fs_jac_phase3<NL, KPT>(tid, nthr, o, s, gw, C, n_params, 1 + which, J, ldj);
+        }
+    }
+}
+
+// jac [B * P, ldj]: the P derivative rows of every point, contiguous per point (ldj >= k_pad; columns [0, k_pad) of every row are written)
+void dl_launch_fullshape_jac(const DlObsDev* obs_host, int n_obs, const DlObsDev* obs_dev, const double* theta, int n_params, int64_t B, int k_live, int k_pad, double* jac, int64_t ldj,
+                             hipStream_t stream) {
+    size_t shm = 0;
+    bool nl3 = true;
+    for (int i = 0; i < n_obs; ++i) { shm = std::max(shm, dl_fs_jac_shared_doubles(obs_host[i], n_params) * sizeof(double)); nl3 = nl3 && obs_host[i].n_ell <= 3; }
+    auto launch = [&](auto kernel) {
+        if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        DL_LAUNCH(kernel, dim3((unsigned)B, (unsigned)n_obs), dim3(DL_FS_THREADS), shm, stream, obs_dev, theta, n_params, k_live, k_pad, jac, ldj);
+    };
+    if (nl3) launch(dl_fullshape_jac_kernel<3, 2>); else launch(dl_fullshape_jac_kernel<DL_MAX_ELL, 1>);
 }
 
 // BAO wiggle model: one workgroup per point; constant splines read from global memory, no per-point spline build.  One kernel per wiggle model: registers are

@@ -2,7 +2,8 @@
 
 ``Fisher(likelihood)(**center)`` evaluates the theory vector on the whole finite-difference stencil of the varied parameters as ONE GPU
 batch (the reference's ``Differentiation`` scatters the stencil points over MPI ranks, differentiation.py:394-398) and ``dl_eval_fisher``
-(csrc/dl_fisher.hip) forms ``d(flatdiff)/d(theta)`` by central differences of step ``Parameter.delta`` and the reference's Gaussian finalisation
+(csrc/dl_fisher.hip) forms ``d(flatdiff)/d(theta)`` by central differences of step ``Parameter.delta`` (or, ``method='analytic'``, takes it exactly from the
+theory's Jacobian kernel, csrc/dl_fullshape_jac.h: ``dl_eval_fisher_analytic``) and the reference's Gaussian finalisation
 (fisher.py:731-750) on the device: ``hessian = -dD P dD^T``, ``gradient = -dD P D``, ``offset = -D P D`` (no 1/2, as in the reference, line 746).
 The host adds the Gaussian prior terms (fisher.py:706-716) and keeps the P x P ``LikelihoodFisher`` algebra (216-257).
 """
@@ -70,14 +71,21 @@ class FisherGaussianLikelihood(object):
 
 
 class Fisher(object):
-    """Estimate the Fisher matrix of ``likelihood`` (a Gaussian likelihood of this package) by finite differences, entirely on the GPU: the stencil of all
+    """Estimate the Fisher matrix of ``likelihood`` (a Gaussian likelihood of this package) entirely on the GPU.  ``method='finite'`` (default): the stencil of all
     centres goes through the theory kernels and the whitened window GEMM as one batch and ``dl_eval_fisher`` forms ``offset``, ``gradient`` and ``hessian``
-    (fisher.py:739-748) with an fp64 MFMA Gram product per centre.
+    (fisher.py:739-748) with an fp64 MFMA Gram product per centre.  ``method='analytic'``: ``dl_eval_fisher_analytic`` -- the same algebra on EXACT derivative rows
+    written by the theory's Jacobian kernel (csrc/dl_fullshape_jac.h; what the reference's ``Differentiation`` takes from jax): no step size, one theory row per
+    centre instead of 1 + 2 P; ``NotImplementedError`` outside its scope (:attr:`SCOPE`).  ``'auto'``: analytic where available, else finite.
 
     Analytically solved parameters ('.marg' / '.best' / '.auto' / '.prec') are VARIED, as in the reference, which warns and works on a copy of the likelihood with
     ``derived=False`` for them (fisher.py:688-695)."""
 
-    def __init__(self, likelihood, delta_scale=1.):
+    SCOPE = ('the analytic Fisher covers Kaiser full-shape likelihoods (fixed / ShapeFit template on uniform knots, no damping, no counter terms, no pass-through '
+             'columns, no observable transform; any number of observables; at most 31 parameters): use method="finite"')
+
+    def __init__(self, likelihood, delta_scale=1., method='finite'):
+        if method not in ('finite', 'analytic', 'auto'): raise ValueError('method must be one of finite, analytic, auto')
+        self.method = method
         self.likelihood = likelihood
         likelihood.initialize()
         self.delta_scale = float(delta_scale)
@@ -119,6 +127,13 @@ class Fisher(object):
         centers = np.ascontiguousarray(np.atleast_2d(centers), dtype='f8')
         ctx = self._get_context()
         device = torch.device('cuda', ctx.device)
+        if self.method != 'finite':
+            # exact derivative rows (dl_eval_fisher_analytic): no steps, one theory row per centre; None: outside the Jacobian kernel's scope, the context decides
+            out = ctx.eval_fisher_analytic(torch.as_tensor(centers, device=device))
+            if out is not None:
+                hessian, gradient, offset = out
+                return offset.cpu().numpy(), gradient.cpu().numpy(), hessian.cpu().numpy()
+            if self.method == 'analytic': raise NotImplementedError(self.SCOPE)
         hessian, gradient, offset = ctx.eval_fisher(torch.as_tensor(centers, device=device), torch.as_tensor(self.steps(centers), device=device).contiguous())
         return offset.cpu().numpy(), gradient.cpu().numpy(), hessian.cpu().numpy()
 

@@ -95,11 +95,13 @@ def levenberg_marquardt(evaluate, start, lower, upper, max_iterations=100, xtol=
 class GaussNewtonProfiler(BasePosteriorSampler):
     """``GaussNewtonProfiler(likelihood, seed=None, ref_scale=1., save_fn=None).maximize(niterations=4, start=None)`` -- the call surface of the reference's profilers
     (profilers/base.py: ``maximize(niterations, start)``; ``niterations`` = number of independent starts drawn from the parameters' ``ref`` distributions).
-    Analytically solved parameters are varied with the others (as ``Fisher`` does, following the reference: fisher.py:688-695)."""
+    Analytically solved parameters are varied with the others (as ``Fisher`` does, following the reference: fisher.py:688-695).
+    ``derivatives``: the ``method`` of :class:`Fisher` -- 'finite' (default: central differences of step ``Parameter.delta``, 1 + 2 P theory rows per candidate),
+    'analytic' (exact derivative rows, one theory row per candidate: the iteration converges to the zero of the true gradient) or 'auto'."""
 
-    def __init__(self, likelihood, save_fn=None, **kwargs):
+    def __init__(self, likelihood, save_fn=None, derivatives='finite', **kwargs):
         super(GaussNewtonProfiler, self).__init__(likelihood, **kwargs)
-        self.fisher = Fisher(likelihood)
+        self.fisher = Fisher(likelihood, method=derivatives)
         self.params = self.fisher.varied_params
         self.save_fn = save_fn
         self.profiles = None

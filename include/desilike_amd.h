@@ -172,6 +172,15 @@ int  dl_eval_logposterior(dl_ctx* ctx, const double* theta_dev, int64_t B, doubl
  * D = flattheory - flatdata.  Outputs (any may be NULL): hessian_dev [B, P, P], gradient_dev [B, P], offset_dev [B].  The context must have no analytically
  * solved parameter (vary them: the reference's Fisher does the same, fisher.py:688-695); P <= 31.  Asynchronous on ``hip_stream``. */
 int  dl_eval_fisher(dl_ctx* ctx, const double* centers_dev, const double* steps_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, void* hip_stream);
+/* The same Fisher algebra from EXACT derivatives (what the reference's Differentiation takes from jax when it is present, desilike/differentiation.py; the
+ * finalisation of fisher.py:731-750 then works on an exact dD): dD = W~ . d(theory vector) / d theta, the rows d(theory vector) / d theta_p written by the
+ * forward-mode twin of the gradient kernel (csrc/dl_fullshape_jac.h: qpar / qper through every AP mode, df, dm, dn, b1 of either tracer, sn0) -- no steps, one theory
+ * row per centre instead of 1 + 2 P.  offset, gradient, hessian as dl_eval_fisher (no 1/2); outputs (any may be NULL): hessian_dev [B, P, P], gradient_dev [B, P],
+ * offset_dev [B]; NaN inputs give NaN outputs for their centre.  Returns 0; 1 on error; 2 -- nothing launched -- outside the scope: Kaiser tracers with a fixed or
+ * ShapeFit template on uniform knots, no damping, no counter terms, no pass-through columns (any number of observables), no observable transform, no analytically
+ * solved parameter, P <= 31 (use dl_eval_fisher then).  Works in passes over B (at most 2048 centres, and pass x (1 + P) x max(K_pad, N_pad) <= 16 Mi doubles); work
+ * buffers grow on demand and are freed with the context: nothing allocates once they are warm.  Asynchronous on ``hip_stream``. */
+int  dl_eval_fisher_analytic(dl_ctx* ctx, const double* centers_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, void* hip_stream);
 /* log-posterior [B] and its ANALYTIC gradient [B, P] (what the reference's gradient-based samplers take from jax.value_and_grad: desilike/samplers/hmc.py:194,
  * samplers/nuts.py:205): d logL / d theta = Y . d(theory vector) / d theta with Y = -W~^T d~, the derivative contracted on the fly by the theory's gradient kernel
  * (qpar / qper through every AP mode, df, dm, dn, b1 of either tracer, sn0; the spline of the template is linear in its data, so d / d dm is the spline of

@@ -72,6 +72,17 @@ SYMBOLS = {
     'dl_nuts_set_adaptation': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
     'dl_nuts_run': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_nuts_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
+    'dl_mclmc_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_uint64,
+                                       ctypes.c_double, ctypes.c_int32, _c_double_p, _c_double_p]),
+    'dl_mclmc_destroy': (None, [ctypes.c_void_p]),
+    'dl_mclmc_set_preconditioner': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int32, ctypes.c_void_p]),
+    'dl_mclmc_set_hyper': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    'dl_mclmc_set_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
+    'dl_mclmc_get_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), _c_double_p, ctypes.c_void_p]),
+    'dl_mclmc_set_adaptation': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    'dl_mclmc_get_moments': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_void_p]),
+    'dl_mclmc_run': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_mclmc_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
     'dl_mlp_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int32, _c_int32_p, ctypes.c_int32, _c_double_p]),
     'dl_mlp_destroy': (None, [ctypes.c_void_p]),
     'dl_mlp_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
@@ -845,6 +856,98 @@ class DeviceNUTS(object):
     def close(self):
         if getattr(self, '_handle', None):
             self._lib.dl_nuts_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceMCLMC(object):
+    """Owner of one ``dl_mclmc`` (include/desilike_amd.h): ``nchains`` microcanonical Langevin chains resident on the GPU of ``ctx``, one (isokinetic_leapfrog) or two
+    (isokinetic_mclachlan) gradient batches per step.  ``gradient``, ``fd_delta``, ``fd_limits`` as :class:`DeviceNUTS`."""
+    MODES = DeviceNUTS.MODES
+    INTEGRATORS = {'isokinetic_leapfrog': 0, 'isokinetic_mclachlan': 1}
+
+    def __init__(self, ctx, nchains, chain_ids=None, integrator='isokinetic_mclachlan', seed=0, offset=0., gradient='auto', fd_delta=None, fd_limits=None):
+        lib = load()
+        if ctx.expand is not None:
+            raise NotImplementedError('the device-resident sampler moves in the columns of the device context: parameters derived by an expression need the host-driven sampler')
+        if isinstance(integrator, str):
+            if integrator not in self.INTEGRATORS: raise ValueError('integrator must be one of {}, found {!r}'.format(sorted(self.INTEGRATORS), integrator))
+            integrator = self.INTEGRATORS[integrator]
+        P = ctx.n_params
+        chain_ids = np.ascontiguousarray(np.arange(nchains) if chain_ids is None else chain_ids, dtype='i4')
+        if len(chain_ids) != nchains: raise ValueError('chain_ids must have one entry per chain')
+        fd_delta = None if fd_delta is None else np.ascontiguousarray(fd_delta, dtype='f8').reshape(P, 2)
+        fd_limits = None if fd_limits is None else np.ascontiguousarray(fd_limits, dtype='f8').reshape(P, 2)
+        handle = ctypes.c_void_p()
+        if lib.dl_mclmc_create(ctypes.byref(handle), ctx._handle, int(nchains), chain_ids.ctypes.data_as(_c_int32_p), int(integrator), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                               float(offset), self.MODES[gradient], _f64_ptr(fd_delta), _f64_ptr(fd_limits)) != 0:
+            raise LibraryError(lib.dl_last_error(None).decode())
+        self._lib, self._handle, self._ctx = lib, handle, ctx     # (the context must outlive the sampler)
+        self.nchains, self.n_params, self.device = int(nchains), P, ctx.device
+
+    _check, _stream = DeviceNUTS._check, DeviceNUTS._stream
+
+    def info(self, key):
+        return int(self._lib.dl_mclmc_info(self._handle, key.encode()))
+
+    def set_preconditioner(self, factor, stream=None):
+        """A of x = x^ + A z: its diagonal [P] or a lower triangular factor [P, P]."""
+        factor = np.ascontiguousarray(factor, dtype='f8')
+        if factor.shape not in [(self.n_params,), (self.n_params,) * 2]: raise ValueError('factor must have shape ({0:d},) or ({0:d}, {0:d})'.format(self.n_params))
+        self._check(self._lib.dl_mclmc_set_preconditioner(self._handle, _f64_ptr(factor), int(factor.ndim == 2), self._stream(stream)))
+
+    def set_hyper(self, step_size, L, stream=None):
+        self._check(self._lib.dl_mclmc_set_hyper(self._handle, float(step_size), float(L), self._stream(stream)))
+
+    def set_state(self, coords, momenta=None, logposterior=None, counters=None, stream=None):
+        coords = np.ascontiguousarray(coords, dtype='f8')
+        if coords.shape != (self.nchains, self.n_params):
+            raise ValueError('coords must have shape ({:d}, {:d}), found {}'.format(self.nchains, self.n_params, coords.shape))
+        momenta = None if momenta is None else np.ascontiguousarray(momenta, dtype='f8').reshape(self.nchains, self.n_params)
+        logposterior = None if logposterior is None else np.ascontiguousarray(logposterior, dtype='f8').reshape(self.nchains)
+        counters = None if counters is None else np.ascontiguousarray(counters, dtype='i8').reshape(self.nchains)
+        self._check(self._lib.dl_mclmc_set_state(self._handle, _f64_ptr(coords), _f64_ptr(momenta), _f64_ptr(logposterior),
+                                                 None if counters is None else counters.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self._stream(stream)))
+
+    def get_state(self, stream=None):
+        """(points [nchains, P], momenta [nchains, P], log-posteriors, step counters, step sizes) as numpy arrays; synchronises."""
+        coords, momenta = np.empty((self.nchains, self.n_params)), np.empty((self.nchains, self.n_params))
+        logp, eps, counters = np.empty(self.nchains), np.empty(self.nchains), np.empty(self.nchains, dtype='i8')
+        self._check(self._lib.dl_mclmc_get_state(self._handle, _f64_ptr(coords), _f64_ptr(momenta), _f64_ptr(logp), counters.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                 _f64_ptr(eps), self._stream(stream)))
+        return coords, momenta, logp, counters, eps
+
+    def set_adaptation(self, step_size_on, moments_on=False, desired_energy_var=5e-4, trust_in_estimate=1.5, num_effective_samples=150., stream=None):
+        self._check(self._lib.dl_mclmc_set_adaptation(self._handle, int(bool(step_size_on)), int(bool(moments_on)), float(desired_energy_var), float(trust_in_estimate),
+                                                      float(num_effective_samples), self._stream(stream)))
+
+    def get_moments(self, stream=None):
+        """Per chain (sum w [nchains], sum w x [nchains, P], sum w x^2 [nchains, P]); synchronises."""
+        sw, sx, sxx = np.empty(self.nchains), np.empty((self.nchains, self.n_params)), np.empty((self.nchains, self.n_params))
+        self._check(self._lib.dl_mclmc_get_moments(self._handle, _f64_ptr(sw), _f64_ptr(sx), _f64_ptr(sxx), self._stream(stream)))
+        return sw, sx, sxx
+
+    def buffers(self, quota):
+        """Record buffers of one batch: coords [nchains, quota, P], logposterior [nchains, quota], info [nchains, quota, 3], count [nchains] (zeroed)."""
+        import torch
+        device = torch.device('cuda', self.device)
+        return (torch.empty((self.nchains, quota, self.n_params), dtype=torch.float64, device=device), torch.empty((self.nchains, quota), dtype=torch.float64, device=device),
+                torch.empty((self.nchains, quota, 3), dtype=torch.float64, device=device), torch.zeros(self.nchains, dtype=torch.int32, device=device))
+
+    def run(self, nsteps, quota, buffers, thin_by=1, stream=None):
+        """Enqueue ``nsteps`` integrator steps of every chain into the record ``buffers`` of a batch of ``quota`` records per chain (asynchronous)."""
+        coords, logp, info, count = buffers
+        self._check(self._lib.dl_mclmc_run(self._handle, int(nsteps), int(quota), int(thin_by), ctypes.c_void_p(coords.data_ptr()), ctypes.c_void_p(logp.data_ptr()),
+                                           ctypes.c_void_p(info.data_ptr()), ctypes.c_void_p(count.data_ptr()), self._stream(stream)))
+
+    def close(self):
+        if getattr(self, '_handle', None):
+            self._lib.dl_mclmc_destroy(self._handle)
             self._handle = None
 
     def __del__(self):

@@ -1034,4 +1034,7 @@ def __getattr__(name):
     if name == 'NUTSSampler':
         from . import nuts
         return nuts.NUTSSampler
+    if name == 'MCLMCSampler':
+        from . import mclmc
+        return mclmc.MCLMCSampler
     raise AttributeError('module {!r} has no attribute {!r}'.format(__name__, name))

@@ -363,6 +363,48 @@ int  dl_nuts_run(dl_nuts* nuts, int64_t nsteps, int32_t quota, int32_t thin_by, 
  * "dense", "adapt" */
 int64_t dl_nuts_info(const dl_nuts* nuts, const char* key);
 
+/* ---- device-resident microcanonical Langevin sampler ------------------------------------------------------------------------------------------
+ * The reference's MCLMCSampler (desilike/samplers/mclmc.py: blackjax.mclmc; Robnik et al. arXiv:2212.08549) on ``nchains`` chains resident on the GPU (csrc/dl_mclmc.h
+ * states the algorithm, the rule for a step that leaves the support and the random draws).  No accept / reject, no tree: a step of every chain is one
+ * (isokinetic_leapfrog) or two (isokinetic_mclachlan) stages, each one gradient batch of the pending positions and one kernel; between two calls every chain rests
+ * at a step boundary.  Nothing in dl_mclmc_run allocates or synchronises.  Errors: non-zero, message via dl_last_error(NULL). */
+typedef struct dl_mclmc dl_mclmc;
+/* chain_ids[nchains] global index of every chain (NULL: 0 .. nchains - 1; keys the draws: a chain is the same on any rank); integrator 0 isokinetic_leapfrog,
+ * 1 isokinetic_mclachlan; offset, gradient_mode, fd_delta, fd_limits as dl_nuts_create.  The context has 2 .. 64 parameters (d = 1 has no isokinetic dynamics). */
+int  dl_mclmc_create(dl_mclmc** out, dl_ctx* ctx, int32_t nchains, const int32_t* chain_ids, int32_t integrator, uint64_t seed, double offset, int32_t gradient_mode,
+                     const double* fd_delta, const double* fd_limits);
+void dl_mclmc_destroy(dl_mclmc* mclmc);
+/* preconditioner A of x = x^ + A z (host): its positive diagonal [P] (dense = 0; blackjax's sqrt_diag_cov) or a lower triangular factor [P, P] with a positive
+ * diagonal (dense = 1: the Cholesky factor of a covariance; entries above the diagonal are not read); synchronises */
+int  dl_mclmc_set_preconditioner(dl_mclmc* mclmc, const double* factor, int32_t dense, void* hip_stream);
+/* step size of every chain (replaces the adapted ones) and momentum decoherence length L (+inf: no refresh), both in the preconditioned coordinates; synchronises */
+int  dl_mclmc_set_hyper(dl_mclmc* mclmc, double step_size, double L, void* hip_stream);
+/* host arrays: coords[nchains, P] (finite), momenta[nchains, P] unit vectors (NULL: z / |z| drawn from the chain's counter), logposterior[nchains] (NULL: evaluated
+ * here with the gradient, which is evaluated in any case; must be finite), step_counters[nchains] (NULL: 0) -- the counter that keys each chain's draws (resume);
+ * synchronises */
+int  dl_mclmc_set_state(dl_mclmc* mclmc, const double* coords, const double* momenta, const double* logposterior, const int64_t* step_counters, void* hip_stream);
+/* host arrays (any may be NULL): current points [nchains, P], momenta [nchains, P], log-posteriors, step counters and per chain the step size in use; synchronises */
+int  dl_mclmc_get_state(dl_mclmc* mclmc, double* coords, double* momenta, double* logposterior, int64_t* step_counters, double* step_size, void* hip_stream);
+/* step_size_on != 0: the per-chain energy-variance controller restarts (a = b = 0, no cap) and runs from the next step on: xi = dE^2 / (d desired_energy_var) + 1e-8,
+ * w = exp(-(log xi / (6 trust_in_estimate))^2 / 2), a <- gamma a + w xi / eps^6, b <- gamma b + w, gamma = (num_effective_samples - 1) / (num_effective_samples + 1),
+ * eps <- (a / b)^(-1/6); an undone step sets eps <- 0.8 eps and caps eps there; 0: the step sizes stay as they are.  moments_on != 0: the per-chain sums of
+ * dl_mclmc_get_moments restart and accumulate; 0: they stay as they are.  synchronises */
+int  dl_mclmc_set_adaptation(dl_mclmc* mclmc, int32_t step_size_on, int32_t moments_on, double desired_energy_var, double trust_in_estimate, double num_effective_samples,
+                             void* hip_stream);
+/* host arrays (any may be NULL): per chain sum w [nchains], sum w x [nchains, P], sum w x^2 [nchains, P], w = the step size in use, over the steps that were not
+ * undone while moments_on; synchronises */
+int  dl_mclmc_get_moments(dl_mclmc* mclmc, double* sum_w, double* sum_wx, double* sum_wxx, void* hip_stream);
+/* ``nsteps`` integrator steps of every chain, enqueued on ``hip_stream`` (asynchronous).  Every ``thin_by``-th step of a chain (by its step counter) is recorded into
+ * slot out_count_dev[c] of out_coords_dev[nchains, quota, P], out_logp_dev[nchains, quota] (offset included), out_info_dev[nchains, quota, 3] (energy change dE,
+ * flag -- 1: the step left the support and was undone --, step size in use) and the count incremented; a chain whose count reached ``quota`` rests (its row is still
+ * evaluated and ignored).  The counts are NOT reset: the caller zeroes them at the start of a batch and calls dl_mclmc_run with the same buffers until every count
+ * is ``quota`` (how the calls are chunked does not change the chains). */
+int  dl_mclmc_run(dl_mclmc* mclmc, int64_t nsteps, int32_t quota, int32_t thin_by, double* out_coords_dev, double* out_logp_dev, double* out_info_dev,
+                  int32_t* out_count_dev, void* hip_stream);
+/* integer properties: "nchains", "n_params", "steps" (integrator steps enqueued so far), "integrator", "gradients_per_step", "finite" (1 once central differences
+ * are in use), "dense", "adapt", "moments" */
+int64_t dl_mclmc_info(const dl_mclmc* mclmc, const char* key);
+
 /* ---- MLP emulator training ---------------------------------------------------------------------------------------
  * The reference trains its MLP emulators through the third-party engine ``cosmoprimo.emulators.tools.MLPEmulatorEngine`` (desilike/emulators/__init__.py:510-533;
  * network structure: emulators/conversion.py:20-96).  Here: fp64 mini-batch Adam on the mean squared error of the (already scaled) outputs, entirely on the device

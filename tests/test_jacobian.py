@@ -12,7 +12,7 @@ APMODES = {0: '', 1: 'qiso', 2: 'qap', 3: 'qisoqap'}
 
 def oracle_theory(g, names, row, apmode=0):
     """The concatenated theory vector (every observable's [n_ell, n_kin] block, flattened) of the oracle at one theta row."""
-    p = dict(zip(names, row))
+    p = dict(g.get('fixed', {}), **dict(zip(names, row)))
     if apmode: p['qpar'], p['qper'] = orc.ap_qparqper(APMODES[apmode], 1. / 3., **p)
     blocks, iobs = [], 0
     while 'obs{:d}'.format(iobs) in g:
@@ -42,12 +42,21 @@ def stencil_jacobian(theory, theta):
 
 def make_case(case):
     """(golden, names, spec, theta, apmode) of a named case; the AP modes reinterpret the first two theta columns of the config-2 fixture."""
-    if case in ('cfg2', 'cfg2_dn', 'qiso', 'qap', 'qisoqap'):
+    if case in ('cfg2', 'cfg2_dn', 'cfg2_dn_only', 'cfg2_ells5', 'qiso', 'qap', 'qisoqap'):
         g = load_golden('cfg2_shapefit_window')
     elif case == 'cfg5':
         g = load_golden('cfg5_two_tracers')
     else:
         g = load_golden('cfg1_kaiser_nowindow')
+    if case == 'cfg2_ells5':                                                       # five multipoles: the NL = 5 accumulators; the window reads nothing of the two new blocks
+        from numpy.polynomial import legendre as npleg
+        c = g['obs0']
+        assert tuple(c['ellsin']) == (0, 2, 4)
+        wmu = c['wmu_ell'][0]                                                      # (ell = 0: the bare Gauss-Legendre weights)
+        c['wmu_ell'] = np.vstack([c['wmu_ell']] + [wmu * (2 * ell + 1) * npleg.legval(c['mu'], [0.] * ell + [1.]) for ell in (6, 8)])
+        c['ellsin'] = np.array([0, 2, 4, 6, 8])
+        c['matrix_full'] = np.hstack([c['matrix_full'], np.zeros((c['matrix_full'].shape[0], 2 * c['kin'].size))])
+        c['shotnoisein'] = np.append(c['shotnoisein'], [0., 0.])
     names = [str(n) for n in g['names']]
     spec = spec_from_golden(g)
     theta = g['theta'][:2].copy()
@@ -67,6 +76,11 @@ def make_case(case):
         spec['priors'] = np.vstack([spec['priors'], [0., -0.5, 0.5, 0., 1.]])
         inputs['dn'] = (P, 0.)
         theta = np.column_stack([theta, [0.02, -0.03]])
+    if case == 'cfg2_dn_only':                                                     # dm fixed at 0.01, dn sampled in its column: pass 1 is skipped, pass 2 runs
+        idm = names.index('dm')
+        names[idm] = 'dn'
+        inputs['dm'], inputs['dn'] = (-1, 0.01), (idm, 0.)
+        g['fixed'] = {'dm': 0.01}
     if case == 'fixed':                                                            # fixed template: the dm column reaches nothing
         spec['observables'][0]['template'] = np.array([0])
         inputs['dm'] = (-1, 0.)
@@ -74,7 +88,7 @@ def make_case(case):
     return g, names, spec, theta, apmode
 
 
-CASES = ['cfg2', 'cfg5', 'cfg2_dn', 'qiso', 'qap', 'qisoqap', 'fixed']
+CASES = ['cfg2', 'cfg5', 'cfg2_dn', 'cfg2_dn_only', 'cfg2_ells5', 'qiso', 'qap', 'qisoqap', 'fixed']
 
 
 @pytest.mark.parametrize('case', CASES)
@@ -140,7 +154,7 @@ def test_jacobian_under_sanitizers():
     here = os.path.dirname(os.path.abspath(__file__))
     code = ('import sys; sys.path.insert(0, {here!r}); sys.path.insert(0, {root!r})\n'
             'import test_jacobian as t\n'
-            'for case in ["cfg5", "cfg2_dn", "qisoqap", "fixed"]: t.test_jacobian_contracted_equals_gradient_phase(case)\n'
+            'for case in ["cfg5", "cfg2_dn", "cfg2_dn_only", "cfg2_ells5", "qisoqap", "fixed"]: t.test_jacobian_contracted_equals_gradient_phase(case)\n'
             't.test_jacobian_out_of_scope()\n'
             'print("sanitized jacobian ok")\n').format(here=here, root=os.path.dirname(here))
     env = dict(os.environ, LD_PRELOAD=libasan, ASAN_OPTIONS='detect_leaks=0:abort_on_error=0:halt_on_error=1', UBSAN_OPTIONS='print_stacktrace=1:halt_on_error=1', DL_EMULATION_SANITIZE='1')

@@ -225,6 +225,7 @@ class Context(object):
         self.n_params, self.n_data, self.n_obs, self.n_solved = (self.info(name) for name in ['n_params', 'n_data', 'n_obs', 'n_solved'])
         # parameters derived from others by an expression (parameter.py:758-807) are extra theta columns of the device context, computed here from the caller's
         # columns: ``expand(theta [B, n_params]) -> [B, n_device_params]`` (numpy array or torch tensor, whatever it is given), set by the likelihood
+        self.emulated = any('emu0' in obs for obs in spec.get('observables', []))   # an emulated theory (dl_emu_jac.h is its analytic Jacobian)
         self.n_device_params, self.expand = self.n_params, None
         if spec.get('_expand', None) is not None:
             self.set_expand(*spec['_expand'])
@@ -431,9 +432,10 @@ class Context(object):
         return hessian, gradient, offset
 
     def eval_fisher_analytic(self, centers, hessian=None, gradient=None, offset=None, stream=None):
-        """The Fisher algebra from exact derivative rows (``dl_eval_fisher_analytic``; csrc/dl_fullshape_jac.h): ``centers [B, P]`` -> ``(hessian [B, P, P],
+        """The Fisher algebra from exact derivative rows (``dl_eval_fisher_analytic``; csrc/dl_fullshape_jac.h for Kaiser theories, csrc/dl_emu_jac.h for one
+        velocileptors observable on an MLP- or Taylor-emulated PT node with every solved parameter varied): ``centers [B, P]`` -> ``(hessian [B, P, P],
         gradient [B, P], offset [B])`` (float64 device tensors, allocated if ``None``; ``False``: that output is not wanted -- a NULL pointer -- and comes back as
-        ``None``); asynchronous on ``stream``.  Returns ``None`` when the context is outside the Jacobian kernel's scope (the caller uses :meth:`eval_fisher`)."""
+        ``None``); asynchronous on ``stream``.  Returns ``None`` when the context is outside the Jacobian kernels' scope (the caller uses :meth:`eval_fisher`)."""
         import torch
         if stream is None:
             stream = torch.cuda.current_stream(centers.device).cuda_stream

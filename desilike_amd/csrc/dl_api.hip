@@ -80,6 +80,10 @@ struct dl_ctx {
     // analytic Fisher (dl_eval_fisher_analytic): residual rows d~ [cap, N_pad], Jacobian rows [cap P (whole 64-row GEMM tiles), K_pad], their window product (split-K slabs)
     double *fa_resid = nullptr, *fa_jac = nullptr, *fa_rows = nullptr;
     int64_t fa_cap = 0, fa_slab_rows = 0;
+    // analytic Fisher of an emulated observable (dl_emu_jac.h): basis rows [cap (1 + n_xv), nb_pad], U [cap (1 + n_xv), 19, N_pad], monomials [cap, 20] and their
+    // derivatives [cap, P, 20], d~ [cap, N_pad], derivative rows [cap P, N_pad]
+    double *ej_basis = nullptr, *ej_u = nullptr, *ej_c = nullptr, *ej_dc = nullptr, *ej_resid = nullptr, *ej_rows = nullptr;
+    int64_t ej_cap = 0;
     // analytic gradient of an emulated observable (dl_emu_grad.h): transposed folded operator G^T [eg_ngt, 19 N_pad] (rows h < n_basis), U and V [cap, 19, N_pad],
     // Q [cap, 1 + n_var, 19], dJ / d basis [cap, eg_ngt]
     double *eg_gt = nullptr, *eg_u = nullptr, *eg_v = nullptr, *eg_q = nullptr, *eg_gb = nullptr;
@@ -490,6 +494,7 @@ void dl_destroy(dl_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     for (double* p : {ctx->grad_wtT, ctx->grad_zero, ctx->grad_delta, ctx->grad_y, ctx->grad_phys}) if (p) (void)hipFree(p);
     for (double* p : {ctx->fa_resid, ctx->fa_jac, ctx->fa_rows}) if (p) (void)hipFree(p);
+    for (double* p : {ctx->ej_basis, ctx->ej_u, ctx->ej_c, ctx->ej_dc, ctx->ej_resid, ctx->ej_rows}) if (p) (void)hipFree(p);
     for (double* p : {ctx->eg_gt, ctx->eg_u, ctx->eg_v, ctx->eg_q, ctx->eg_gb, ctx->eg_wt[0], ctx->eg_wt[1], ctx->eg_wt[2]}) if (p) (void)hipFree(p);
     if (ctx->grad_status) (void)hipFree(ctx->grad_status);
     void* ptrs[] = {ctx->arena_dev, ctx->priors_dev, ctx->wt_white_dev, ctx->wt_frag_dev, ctx->bias_white_dev, ctx->wt_full_dev, ctx->bias_full_dev, ctx->wh_dev,
@@ -508,9 +513,13 @@ void dl_destroy(dl_ctx* ctx) {
     delete ctx;
 }
 
+static bool dl_fisher_emu_in_scope(const dl_ctx* ctx);
+static int64_t dl_fisher_emu_per_pass(const dl_ctx* ctx);
+
 int64_t dl_info(const dl_ctx* ctx, const char* key) {
     if (!ctx || !key) return -1;
     std::string k(key);
+    if (k == "fisher_analytic_pass") return dl_fisher_emu_in_scope(ctx) ? dl_fisher_emu_per_pass(ctx) : -1;   // centres per pass of the emulated branch of dl_eval_fisher_analytic
     if (k == "n_params") return ctx->n_params;
     if (k == "n_data") return ctx->n_data;
     if (k == "n_obs") return ctx->n_obs;
@@ -792,11 +801,66 @@ int dl_eval_fisher(dl_ctx* ctx, const double* centers_dev, const double* steps_d
 
 // Fisher algebra from EXACT derivative rows (dl_fullshape_jac.h).  Per pass: theory -> chi2 GEMM with the residual output (d~; its partial chi2 are not used) -> Jacobian
 // kernel (pass x P rows) -> tiled window GEMM of those rows against W~ (no bias: the derivative of the residual) -> Gram kernel on [d~; D~_1 .. D~_P].
-// Returns 2 (nothing launched) outside the scope of the Jacobian kernel.
+// Returns 2 (nothing launched) outside the scope of the Jacobian kernels.
+// Emulated observable (dl_emu_jac.h), per pass: tangent kernel (basis rows, monomials and their derivatives) -> U = G . basis rows (MFMA, (1 + n_xv) rows per centre) ->
+// row kernel (d~ and D~_p) -> Gram kernel on [d~; D~_1 .. D~_P].
+static bool dl_fisher_emu_in_scope(const dl_ctx* ctx) {
+    return ctx->feat_ok && !ctx->any_transform && ctx->n_solved == 0 && ctx->n_obs == 1 && !ctx->any_stacked && ctx->n_params <= 31 &&
+           dl_emu_jac_applicable(ctx->obs_kernarg[0], ctx->N_pad, ctx->n_params) && dl_fisher_waves(ctx->n_white, ctx->n_params, nullptr, nullptr) >= 1;
+}
+
+static int64_t dl_fisher_emu_per_pass(const dl_ctx* ctx) {
+    // centres per pass: pass x max((1 + n_xv) x 19 x N_pad (the U rows), (1 + P) x N_pad (the rows of X)) <= 16 Mi doubles -- the rule of the Kaiser branch, with the
+    // largest buffer of this one in the place of the Jacobian rows --, at most 2048, in whole 64-row tiles
+    const int64_t per_centre = std::max<int64_t>((int64_t)(1 + dl_emu_jac_n_xv(ctx->obs_kernarg[0])) * DL_FG_NM * ctx->N_pad, (int64_t)(1 + ctx->n_params) * ctx->N_pad);
+    return std::max<int64_t>(64, std::min<int64_t>(2048, ((int64_t)16 << 20) / per_centre) / 64 * 64);
+}
+
+static int dl_eval_fisher_analytic_emu(dl_ctx* ctx, const double* centers_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, hipStream_t stream) {
+    const int P = ctx->n_params, Np = ctx->N_pad;
+    const DlObsDev& o = ctx->obs_kernarg[0];
+    const int64_t R = 1 + dl_emu_jac_n_xv(o), K = (int64_t)DL_FG_NM * Np;
+    dl_prof_events.start = dl_prof_events.stop = nullptr;
+    const int64_t per_pass = dl_fisher_emu_per_pass(ctx);
+    const int64_t need = std::min<int64_t>(B, per_pass);
+    if (need > ctx->ej_cap) {
+        if (ctx->ej_cap > 0) DL_HIP_CHECK(ctx, hipDeviceSynchronize());   // (kernels of earlier calls may still use the buffers about to be freed)
+        for (double** p : {&ctx->ej_basis, &ctx->ej_u, &ctx->ej_c, &ctx->ej_dc, &ctx->ej_resid, &ctx->ej_rows}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+        ctx->ej_cap = 0;
+        const int64_t cap = std::min<int64_t>(std::max<int64_t>((need + 63) / 64 * 64, 256), per_pass);
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ej_basis, (size_t)cap * R * o.nb_pad * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ej_u, (size_t)cap * R * K * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ej_c, (size_t)cap * DL_FG_MONO_LD * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ej_dc, (size_t)cap * P * DL_FG_MONO_LD * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ej_resid, (size_t)cap * Np * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ej_rows, (size_t)cap * P * Np * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipDeviceSynchronize());
+        ctx->ej_cap = cap;
+    }
+    for (int64_t b0 = 0; b0 < B; b0 += per_pass) {
+        const int64_t nc = std::min<int64_t>(per_pass, B - b0);
+        const double* th = centers_dev + (size_t)b0 * P;
+        dl_launch_emu_jac_tangent(o, th, P, nc, ctx->ej_basis, ctx->ej_c, ctx->ej_dc, stream);
+        dl_launch_emu_grad_u(ctx->ej_basis, o.nb_pad, 0, o.nb_pad, ctx->gfrag_dev[0], ctx->ej_u, Np, Np, nc * R, stream);
+        dl_launch_emu_jac_rows(o, ctx->ej_u, Np, ctx->ej_c, ctx->ej_dc, ctx->bias_white_dev, P, ctx->n_white, Np, ctx->ej_resid, Np, ctx->ej_rows, Np, nc, stream);
+        dl_launch_fisher_rows(ctx->ej_resid, Np, ctx->ej_rows, Np, ctx->n_white, 1, 0, P, nc, hessian_dev ? hessian_dev + (size_t)b0 * P * P : nullptr,
+                              gradient_dev ? gradient_dev + (size_t)b0 * P : nullptr, offset_dev ? offset_dev + b0 : nullptr, stream);
+    }
+    DL_HIP_CHECK(ctx, hipGetLastError());
+    return 0;
+}
+
 int dl_eval_fisher_analytic(dl_ctx* ctx, const double* centers_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, void* hip_stream) {
     if (!ctx) { g_last_error = "dl_eval_fisher_analytic: null context"; return 1; }
     if (B < 0 || (B > 0 && !centers_dev)) return dl_fail(ctx, "dl_eval_fisher_analytic: invalid argument");
     const int P = ctx->n_params, Np = ctx->N_pad, Kp = ctx->K_pad;
+    // emulated: one observable on the feature path, MLP / Taylor engines, the solved parameters varied (dl_emu_jac.h)
+    if (dl_fisher_emu_in_scope(ctx)) {
+        if (B == 0) return 0;
+        DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+        if (dl_order_streams(ctx, (hipStream_t)hip_stream)) return 1;
+        return dl_eval_fisher_analytic_emu(ctx, centers_dev, B, hessian_dev, gradient_dev, offset_dev, (hipStream_t)hip_stream);
+    }
     if (ctx->feat_ok || ctx->any_transform || ctx->n_solved != 0 || P > 31 || !dl_grad_applicable(ctx->obs_kernarg.data(), ctx->n_obs) ||
         dl_fisher_waves(ctx->n_white, P, nullptr, nullptr) < 1) return 2;
     if (B == 0) return 0;

@@ -159,5 +159,13 @@ void dl_launch_emu_grad_adjoint(const double* feat, int64_t feat_ld, int64_t fea
 void dl_launch_emu_grad_backprop(const DlObsDev& obs, const double* theta, int n_params, const double* priors, const double* gb, int64_t ldg, int n_slabs, int64_t slab_stride,
                                  const double* Q, const int32_t* status, const double* const* wT /* [3]: transposed MLP kernels per engine */, double* grad, int64_t B,
                                  hipStream_t stream);
+// analytic Jacobian of one emulated observable on the feature path (dl_emu_jac.h): per centre the basis and its tangents ((1 + n_xv) rows of nb_pad doubles: the records
+// dl_launch_emu_grad_u reads with feat_ld = nb_pad, feat_off = 0), the monomials cmono [B][20] and their derivatives dmono [B][P][20]; then X = [d~; D~_1 .. D~_P] from
+// U [B (1 + n_xv)][19][ldu]: resid [B][ldr], rows [B P][ld], columns [n_live, N_pad) zero
+bool dl_emu_jac_applicable(const DlObsDev& obs, int N_pad, int n_params);
+int dl_emu_jac_n_xv(const DlObsDev& obs);   // emulator inputs that are theta columns
+void dl_launch_emu_jac_tangent(const DlObsDev& obs, const double* theta, int n_params, int64_t B, double* basis_rows, double* cmono, double* dmono, hipStream_t stream);
+void dl_launch_emu_jac_rows(const DlObsDev& obs, const double* U, int64_t ldu, const double* cmono, const double* dmono, const double* bias, int n_params, int n_live, int N_pad,
+                            double* resid, int64_t ldr, double* rows, int64_t ld, int64_t B, hipStream_t stream);
 // last-error string of the C ABI (thread-local, read by dl_last_error(NULL)); set by translation units other than dl_api.hip
 void dl_set_last_error(const char* msg);

@@ -1927,3 +1927,40 @@ void dl_launch_emu_grad_backprop(const DlObsDev& obs, const double* theta, int n
     const DlEgWT w = {{wT[0], wT[1], wT[2]}};
     DL_LAUNCH(dl_emu_grad_backprop_kernel, dim3((unsigned)B), dim3(64), shm, stream, obs, theta, n_params, priors, gb, ldg, n_slabs, slab_stride, Q, status, w, grad, B);
 }
+
+// ---- analytic Jacobian of an emulated observable (dl_emu_jac.h) -------------------------------------------------------------------------------------------------
+#include "dl_emu_jac.h"
+
+int dl_emu_jac_n_xv(const DlObsDev& o) { return dl_ej_cols(o).n_xv; }
+static int dl_ej_nt(int n_xv) { return n_xv <= 4 ? 4 : n_xv <= 8 ? 8 : 16; }   // tangents the kernel is instantiated for
+
+bool dl_emu_jac_applicable(const DlObsDev& o, int N_pad, int n_params) {
+    if (o.theory != 3 || o.n_pass != 0 || o.n_mono != DL_N_MONO || o.n_var != 0 || o.n_x > DL_MAX_X) return false;
+    if (o.eng[0].type != 0 && o.eng[0].type != 1) return false;
+    for (int ie = 1; ie < 3; ++ie) if (o.eng[ie].type != 0 && o.eng[ie].type != 1 && o.eng[ie].type != -1) return false;
+    if (o.n_basis != (o.eng[0].type == 0 ? o.eng[0].widths[o.eng[0].n_layers] + 1 : o.eng[0].n_terms)) return false;
+    if (N_pad % 32 != 0 || o.nb_pad % 8 != 0 || o.nb_pad < o.n_basis) return false;   // (the column blocks of dl_emu_grad_u_kernel)
+    if (dl_ej_tangent_doubles(o, dl_ej_nt(dl_emu_jac_n_xv(o))) * sizeof(double) > 64 * 1024) return false;
+    if ((size_t)(1 + n_params) * DL_FG_MONO_LD * sizeof(double) > 64 * 1024) return false;
+    return (size_t)DL_FG_PTS * dl_fg_lds_stride(o.nb_pad) * sizeof(double) <= 64 * 1024;
+}
+
+void dl_launch_emu_jac_tangent(const DlObsDev& obs, const double* theta, int n_params, int64_t B, double* basis_rows, double* cmono, double* dmono, hipStream_t stream) {
+    const DlEjCols cols = dl_ej_cols(obs);
+    const int nt = dl_ej_nt(cols.n_xv);
+    const size_t shm = dl_ej_tangent_doubles(obs, nt) * sizeof(double);
+    auto launch = [&](auto kernel) {
+        if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        DL_LAUNCH(kernel, dim3((unsigned)B), dim3(64), shm, stream, obs, cols, theta, n_params, basis_rows, cmono, dmono, B);
+    };
+    if (nt == 4) launch(dl_emu_jac_tangent_kernel<4>);
+    else if (nt == 8) launch(dl_emu_jac_tangent_kernel<8>);
+    else launch(dl_emu_jac_tangent_kernel<16>);
+}
+
+void dl_launch_emu_jac_rows(const DlObsDev& obs, const double* U, int64_t ldu, const double* cmono, const double* dmono, const double* bias, int n_params, int n_live, int N_pad,
+                            double* resid, int64_t ldr, double* rows, int64_t ld, int64_t B, hipStream_t stream) {
+    const DlEjCols cols = dl_ej_cols(obs);
+    const size_t shm = (size_t)(1 + n_params) * DL_FG_MONO_LD * sizeof(double);
+    DL_LAUNCH(dl_emu_jac_rows_kernel, dim3((unsigned)B), dim3(128), shm, stream, cols, U, ldu, cmono, dmono, bias, n_params, n_live, N_pad, resid, ldr, rows, ld, B);
+}

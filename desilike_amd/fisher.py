@@ -3,7 +3,7 @@
 ``Fisher(likelihood)(**center)`` evaluates the theory vector on the whole finite-difference stencil of the varied parameters as ONE GPU
 batch (the reference's ``Differentiation`` scatters the stencil points over MPI ranks, differentiation.py:394-398) and ``dl_eval_fisher``
 (csrc/dl_fisher.hip) forms ``d(flatdiff)/d(theta)`` by central differences of step ``Parameter.delta`` (or, ``method='analytic'``, takes it exactly from the
-theory's Jacobian kernel, csrc/dl_fullshape_jac.h: ``dl_eval_fisher_analytic``) and the reference's Gaussian finalisation
+theory's Jacobian kernel, csrc/dl_fullshape_jac.h, or from the forward mode of an emulated PT node, csrc/dl_emu_jac.h: ``dl_eval_fisher_analytic``) and the reference's Gaussian finalisation
 (fisher.py:731-750) on the device: ``hessian = -dD P dD^T``, ``gradient = -dD P D``, ``offset = -D P D`` (no 1/2, as in the reference, line 746).
 The host adds the Gaussian prior terms (fisher.py:706-716) and keeps the P x P ``LikelihoodFisher`` algebra (216-257).
 """
@@ -74,14 +74,19 @@ class Fisher(object):
     """Estimate the Fisher matrix of ``likelihood`` (a Gaussian likelihood of this package) entirely on the GPU.  ``method='finite'`` (default): the stencil of all
     centres goes through the theory kernels and the whitened window GEMM as one batch and ``dl_eval_fisher`` forms ``offset``, ``gradient`` and ``hessian``
     (fisher.py:739-748) with an fp64 MFMA Gram product per centre.  ``method='analytic'``: ``dl_eval_fisher_analytic`` -- the same algebra on EXACT derivative rows
-    written by the theory's Jacobian kernel (csrc/dl_fullshape_jac.h; what the reference's ``Differentiation`` takes from jax): no step size, one theory row per
-    centre instead of 1 + 2 P; ``NotImplementedError`` outside its scope (:attr:`SCOPE`).  ``'auto'``: analytic where available, else finite.
+    written by the theory's Jacobian kernel (csrc/dl_fullshape_jac.h; what the reference's ``Differentiation`` takes from jax) or, for one velocileptors observable on an
+    MLP- / Taylor-emulated PT node, by the forward mode through the emulator and the bias monomials (csrc/dl_emu_jac.h): no step size, one theory row per centre
+    instead of 1 + 2 P; ``NotImplementedError`` outside its scope (:attr:`SCOPE`).  ``'auto'``: analytic where available AND measured faster than the stencil
+    (Kaiser likelihoods: DESIGN.md section 6d; emulated ones: :attr:`AUTO_EMULATED`), else finite.
 
     Analytically solved parameters ('.marg' / '.best' / '.auto' / '.prec') are VARIED, as in the reference, which warns and works on a copy of the likelihood with
     ``derived=False`` for them (fisher.py:688-695)."""
 
     SCOPE = ('the analytic Fisher covers Kaiser full-shape likelihoods (fixed / ShapeFit template on uniform knots, no damping, no counter terms, no pass-through '
-             'columns, no observable transform; any number of observables; at most 31 parameters): use method="finite"')
+             'columns, no observable transform; any number of observables; at most 31 parameters) and ONE velocileptors P_ell observable on an emulated PT node '
+             '(table engine an MLP or a Taylor engine, sigma8 / fsigma8 engines MLP, Taylor or constant; not the stacked layout, not xi_ell, no transform; at most '
+             '31 parameters, the solved ones included): use method="finite"')
+    AUTO_EMULATED = False     # whether 'auto' takes the analytic path on an emulated context: set from the measurement of DESIGN.md section 6f
 
     def __init__(self, likelihood, delta_scale=1., method='finite'):
         if method not in ('finite', 'analytic', 'auto'): raise ValueError('method must be one of finite, analytic, auto')
@@ -127,8 +132,8 @@ class Fisher(object):
         centers = np.ascontiguousarray(np.atleast_2d(centers), dtype='f8')
         ctx = self._get_context()
         device = torch.device('cuda', ctx.device)
-        if self.method != 'finite':
-            # exact derivative rows (dl_eval_fisher_analytic): no steps, one theory row per centre; None: outside the Jacobian kernel's scope, the context decides
+        if self.method == 'analytic' or (self.method == 'auto' and (self.AUTO_EMULATED or not getattr(ctx, 'emulated', False))):
+            # exact derivative rows (dl_eval_fisher_analytic): no steps, one theory row per centre; None: outside the Jacobian kernels' scope, the context decides
             out = ctx.eval_fisher_analytic(torch.as_tensor(centers, device=device))
             if out is not None:
                 hessian, gradient, offset = out

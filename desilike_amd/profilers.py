@@ -97,7 +97,8 @@ class GaussNewtonProfiler(BasePosteriorSampler):
     (profilers/base.py: ``maximize(niterations, start)``; ``niterations`` = number of independent starts drawn from the parameters' ``ref`` distributions).
     Analytically solved parameters are varied with the others (as ``Fisher`` does, following the reference: fisher.py:688-695).
     ``derivatives``: the ``method`` of :class:`Fisher` -- 'finite' (default: central differences of step ``Parameter.delta``, 1 + 2 P theory rows per candidate),
-    'analytic' (exact derivative rows, one theory row per candidate: the iteration converges to the zero of the true gradient) or 'auto'."""
+    'analytic' (exact derivative rows, one theory row per candidate: the iteration converges to the zero of the true gradient; Kaiser likelihoods and one velocileptors
+    observable on an MLP- / Taylor-emulated PT node, ``NotImplementedError`` with :attr:`Fisher.SCOPE` elsewhere) or 'auto'."""
 
     def __init__(self, likelihood, save_fn=None, derivatives='finite', **kwargs):
         super(GaussNewtonProfiler, self).__init__(likelihood, **kwargs)

@@ -178,7 +178,10 @@ int  dl_eval_fisher(dl_ctx* ctx, const double* centers_dev, const double* steps_
  * row per centre instead of 1 + 2 P.  offset, gradient, hessian as dl_eval_fisher (no 1/2); outputs (any may be NULL): hessian_dev [B, P, P], gradient_dev [B, P],
  * offset_dev [B]; NaN inputs give NaN outputs for their centre.  Returns 0; 1 on error; 2 -- nothing launched -- outside the scope: Kaiser tracers with a fixed or
  * ShapeFit template on uniform knots, no damping, no counter terms, no pass-through columns (any number of observables), no observable transform, no analytically
- * solved parameter, P <= 31 (use dl_eval_fisher then).  Works in passes over B (at most 2048 centres, and pass x (1 + P) x max(K_pad, N_pad) <= 16 Mi doubles); work
+ * solved parameter, P <= 31; or ONE emulated velocileptors P_ell observable on the feature path (csrc/dl_emu_jac.h: forward mode through the emulator and the 19 bias
+ * monomials; table engine an MLP or a Taylor engine, sigma8 / fsigma8 engines MLP, Taylor or constant; not the stacked layout), no observable transform, no analytically
+ * solved parameter (create the context with them varied), P <= 31, passes of pass x max((1 + n_xv) x 19 x N_pad, (1 + P) x N_pad) <= 16 Mi doubles with n_xv the emulator
+ * inputs that are theta columns (dl_info "fisher_analytic_pass": centres per pass of this branch, -1 outside it).  Use dl_eval_fisher elsewhere.  Works in passes over B (at most 2048 centres, and pass x (1 + P) x max(K_pad, N_pad) <= 16 Mi doubles); work
  * buffers grow on demand and are freed with the context: nothing allocates once they are warm.  Asynchronous on ``hip_stream``. */
 int  dl_eval_fisher_analytic(dl_ctx* ctx, const double* centers_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, void* hip_stream);
 /* log-posterior [B] and its ANALYTIC gradient [B, P] (what the reference's gradient-based samplers take from jax.value_and_grad: desilike/samplers/hmc.py:194,

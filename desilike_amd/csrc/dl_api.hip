@@ -533,6 +533,7 @@ int64_t dl_info(const dl_ctx* ctx, const char* key) {
         if (k == "n_out_obs" + std::to_string(i)) return ctx->obs[i].n_out;
         if (k == "n_ell_obs" + std::to_string(i)) return ctx->obs[i].dev.n_ell;
         if (k == "n_kin_obs" + std::to_string(i)) return ctx->obs[i].dev.n_kin;
+        if (k == "moment_form_obs" + std::to_string(i)) return ctx->obs[i].dev.moment_form;   // bit 0: eligible for the moment form of the fast theory kernels, bit 1: knot records
     }
     return -1;
 }
@@ -1040,7 +1041,8 @@ int dl_eval_logposterior_grad(dl_ctx* ctx, const double* theta_dev, int64_t B, d
         const int64_t nb = std::min<int64_t>(per_pass, B - b0);
         const double* th = theta_dev + (size_t)b0 * P;
         int32_t* st = status_dev ? status_dev + b0 : ctx->grad_status;      // (the gradient's finalize needs the status whether the caller wants it or not)
-        dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, th, P, nb, ctx->power_ws, ctx->K_pad, nullptr, 0, stream, nullptr, 0, xcd_local ? dl_chi2_gemm_row_tile(nb, Np) : 0, ctx->obs_array_dev);
+        dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, th, P, nb, ctx->power_ws, ctx->K_pad, nullptr, 0, stream, nullptr, 0, xcd_local ? dl_chi2_gemm_row_tile(nb, Np) : 0, ctx->obs_array_dev,
+                            false);   // (the value from the interval polynomials the gradient kernel differentiates)
         dl_launch_chi2_gemm(ctx->power_ws, Kp, ctx->wt_white_dev, Kp, ctx->bias_white_dev, ctx->delta_ws, nb, Np, Kp, nullptr, th, P, ctx->priors_dev, nullptr, nullptr, nullptr, 1, stream,
                             ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data(), ctx->K_live, ctx->grad_delta, Np, ctx->wt_frag_dev);
         dl_launch_finalize_part(ctx->delta_ws, Np / 16, th, P, ctx->priors_dev, nb, logposterior_dev + b0, nullptr, st, 1, stream);

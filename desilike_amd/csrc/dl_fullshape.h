@@ -100,7 +100,8 @@ struct DlObsDev {
     DlInput to_m, to_n, qto, dpto;         // turn-over template (template kind 2): slopes below / above the turn-over, its shift and amplitude (power_template.py:1324-1333)
     double lkto_fid, lpkto_fid;            // log10 of the fiducial turn-over wavenumber, ln of the fiducial power there
     // band template (template kind 3, power_template.py:893-961): P_tt = P_tt_fid (1 + sum_i (dptt_i - 1) tent_i(k)), P_dd = P_tt / f^2
-    int32_t n_band, pad_band;
+    int32_t n_band, moment_form;           // moment_form (fast uniform-knot kernels without counter terms): bit 0: the spline is evaluated from (knot value, moment)
+                                           // records on the exactly uniform grid (knot table uniform to rounding: see dl_host.hpp); bit 1: knot_rec is filled
     DlInput band_in[DL_MAX_BAND];
     const double* band_tab;                // [n_band][n_t] tent functions at the knots
     // tracer-velocity variant of the PNG theory (primordial_non_gaussianity.py:196-330): P = jac fog (b + f mu'^2) (bv f mu' velfac / k') P(k'), fog = sinc(sigmau k') / (1 + sigmas^2 k'^2 mu'^2 / 2)
@@ -164,6 +165,7 @@ struct DlObsDev {
     const double *sp_gf, *sp_gb;                   // [DL_SEG_QMAX, DL_FS_THREADS] warm-up weights of the forward / backward sweeps: term d = 4 q + part of
                                                    // segment seg sits at [q][4 seg + part] (zero beyond the warm-up length / the ends of the system)
     const double *coef_fixed;                      // [n_t, 4] interval polynomials of the fiducial table (fixed templates)
+    const double *knot_rec;                        // [n_t, 2] ShapeFit template with a constant dn: (pk_fid exp(dn sf_lg), sf_th) of a knot in one 16-byte record
     const double *ct_matrix, *sn_matrix;           // [n_ell, n_kin, n_ct], [n_ell, n_kin, n_sn]
     // TNS one-loop theory (kind 4, dl_tns.h): FoG dispersion and the non-linear bias parameters (full_shape.py:865, 957-971); tns_plan: HOST handle of the
     // geometry tables and the per-evaluation workspace (dl_tns.hip), never dereferenced on the device
@@ -226,6 +228,26 @@ DL_HD DlFsShared dl_fs_shared_carve(double* base, int n_t, int n_in, int n_dd0 =
     else { s.y = work; s.M = work + (size_t)n_t; s.z = work + 2 * (size_t)n_t; }
     s.out = work;
     s.pt = work + (n_dd0 < 0 ? dl_fs_work_doubles(n_t, n_in) : dl_fs_work_doubles(n_t, n_in, n_dd0));
+    return s;
+}
+
+// Moment form (DlObsDev::moment_form, fast kernels without counter terms): records (y_j, m_j) [n_t][2] | padded knot values [DL_FIR_PAD + n_t + DL_FIR_PAD] | pt.
+// The convolution reads its sliding window from the contiguous padded copy and writes the records; the evaluation reads (y_j, m_j, y_j+1, m_j+1) as 32 contiguous
+// bytes.  staged: the output tile s.out (aliasing the padded knot values, dead by then) is needed, because the rows carry pass-through columns or derivative rows.
+DL_HD bool dl_fs_mom_direct(const DlObsDev& o) { return o.n_var == 0 && o.n_pass == 0; }   // every thread stores its own multipoles: no output tile
+DL_HD size_t dl_fs_mom_work_doubles(const DlObsDev& o) {
+    size_t w = (size_t)o.n_t + 2 * DL_FIR_PAD;
+    if (!dl_fs_mom_direct(o) && (size_t)o.n_in > w) w = (size_t)o.n_in;
+    return (w + 1) & ~(size_t)1;
+}
+DL_HD size_t dl_fs_mom_shared_doubles(const DlObsDev& o) { return 2 * (size_t)o.n_t + dl_fs_mom_work_doubles(o) + DL_PT_SIZE_FAST; }
+DL_HD DlFsShared dl_fs_shared_carve_mom(double* base, const DlObsDev& o) {
+    DlFsShared s;
+    s.coef = base;                       // the records (16-byte aligned)
+    double* work = base + 2 * (size_t)o.n_t;
+    s.y = work + DL_FIR_PAD; s.M = nullptr; s.z = nullptr;
+    s.out = work;
+    s.pt = work + dl_fs_mom_work_doubles(o);
     return s;
 }
 
@@ -358,6 +380,22 @@ DL_HD void dl_fs_knots(int tid, int nthr, const DlObsDev& o, const double* th, c
     }
 }
 
+// ShapeFit template with a constant dn, from the records DlObsDev::knot_rec (moment form).  kr[it] = record of knot tid + it nthr for it < DL_KNOT_PREF, requested by
+// the caller at the top of the kernel: one round trip to (cold) memory for all rounds instead of one per round; further rounds read here.
+#define DL_KNOT_PREF 3
+DL_HD void dl_fs_knots_rec(int tid, int nthr, const DlObsDev& o, const double* th, const DlFsShared& s, const double (*kr)[2]) {
+    const int n_t = o.n_t;
+    if (tid < 2 * DL_FIR_PAD) s.y[tid < DL_FIR_PAD ? tid - DL_FIR_PAD : n_t + tid - DL_FIR_PAD] = 0.;   // zero padding
+    // power_template.py:749: exp(dm / a * tanh(a * log(k / kp)) + dn * log(k / kp)), the dn factor folded into the table at create
+    const double dm_a = dl_get(o.dm, th) / o.a;
+#pragma unroll
+    for (int it = 0; it < DL_KNOT_PREF; ++it) {
+        const int j = tid + it * nthr;
+        if (j < n_t) s.y[j] = kr[it][0] * exp(dm_a * kr[it][1]);
+    }
+    for (int j = tid + DL_KNOT_PREF * nthr; j < n_t; j += nthr) s.y[j] = o.knot_rec[2 * j] * exp(dm_a * o.knot_rec[2 * j + 1]);
+}
+
 // the whole of phase 0 + 1 in one call (general kernel, host-side constant folding): mu nodes on the last threads, scalars on thread 0
 DL_HD void dl_fs_phase01(int tid, int nthr, const DlObsDev& o, const double* th, const DlFsShared& s) {
     const int mnode = nthr - 1 - tid;
@@ -483,6 +521,8 @@ DL_HD void dl_fs_phase2d(int tid, int nthr, const DlObsDev& o, const DlFsShared&
 // M_1 = r_1 / 6, M_{n-2} = r_{n-2} / 6.  With w = (6 / h^2) sum_e t_|e| y_{j+e} (the solution on the infinite grid; y zero-padded: whatever sits
 // outside the table only feeds the homogeneous part), M_j = w_j + a mu^(j-1) + b mu^(n-2-j), a = r_1 / 6 - w_1, b = r_{n-2} / 6 - w_{n-2}:
 // the correction matters within ~30 knots of either end.  Each thread produces 4 consecutive w_j from one sliding window of 2 D + 4 knot values.
+// MOM (moment form): the result is m_j = M_j h^2 / 6 -- the factor 6 / h^2 drops out -- written beside y_j into the records s.coef[2 j], s.coef[2 j + 1].
+template <bool MOM = false>
 DL_HD void dl_fs_phase2_fir(int tid, int nthr, const DlObsDev& o, const DlFsShared& s) {
     const double T[DL_FIR_D + 1] = DL_FIR_TAPS;
     const int n = o.n_t;
@@ -513,9 +553,15 @@ DL_HD void dl_fs_phase2_fir(int tid, int nthr, const DlObsDev& o, const DlFsShar
 #pragma unroll
             for (int c = 0; c < 4; ++c) cur[c] = nxt[c];
         }
+        if (MOM) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (j0 + q < n) s.M[j0 + q] = acc[q] * scale;
+            for (int q = 0; q < 4; ++q)
+                if (j0 + q < n) { s.coef[2 * (j0 + q)] = s.y[j0 + q]; s.coef[2 * (j0 + q) + 1] = acc[q]; }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (j0 + q < n) s.M[j0 + q] = acc[q] * scale;
+        }
     }
     // the last 2 DL_FIR_PAD + 1 threads (no window to convolve while n <= 4 (nthr - 65)) tabulate mu^k for the end corrections
     for (int k = tid - (nthr - 2 * DL_FIR_PAD - 1); k >= 0 && k <= 2 * DL_FIR_PAD; k += nthr) {
@@ -556,6 +602,48 @@ DL_HD void dl_fs_phase2d_toep(int tid, int nthr, const DlObsDev& o, const DlFsSh
         s.coef[2 * n + 2 * j + 0] = hx * hx * (c2 + 3. * dl * c3);
         s.coef[2 * n + 2 * j + 1] = hx * hx * hx * c3;
     }
+}
+
+// Moment form: end fix-up of the records, run by the 64 lanes of ONE wavefront (lane = tid < 64) beside the per-mu part C.  Lanes 0-31 correct the moments of knots
+// 1 .. DL_FIR_PAD, lanes 32-63 those of knots n-2 .. n-1-DL_FIR_PAD (n >= 4 DL_FIR_PAD: disjoint; |mu|^DL_FIR_PAD = 5e-19: beyond them the correction is below
+// rounding) by a mu^(j-1) + b mu^(n-2-j) (a, b: dl_fs_phase2d_toep, in units of h^2 / 6); lanes 0 and 32 then set m_0, m_{n-1} by the not-a-knot end relations, so
+// that the end intervals need no special case at evaluation.  Every lane reads what it needs (its own knot and the neighbour towards the interior) BEFORE any lane
+// writes: the lanes of a wavefront run in lockstep and its LDS operations complete in order.  Device only: a serial loop over the lanes would read corrected moments.
+#if defined(__HIPCC__)
+__device__ __forceinline__ void dl_fs_mom_fixup(int lane, const DlObsDev& o, const DlFsShared& s) {
+    const int n = o.n_t;
+    double* rec = s.coef;
+    const double a = ((rec[0] - rec[2]) - (rec[2] - rec[4])) * (1. / 6.) - rec[3];
+    const double b = ((rec[2 * (n - 3)] - rec[2 * (n - 2)]) - (rec[2 * (n - 2)] - rec[2 * (n - 1)])) * (1. / 6.) - rec[2 * (n - 2) + 1];
+    const bool left = lane < DL_FIR_PAD;
+    const int i = left ? 1 + lane : n - 2 - (lane - DL_FIR_PAD);     // this lane's knot
+    const int i2 = left ? i + 1 : i - 1;                              // its neighbour towards the interior
+    const double mi = rec[2 * i + 1] + a * dl_fir_mu_pow(s, i - 1) + b * dl_fir_mu_pow(s, n - 2 - i);
+    const double mi2 = rec[2 * i2 + 1] + a * dl_fir_mu_pow(s, i2 - 1) + b * dl_fir_mu_pow(s, n - 2 - i2);
+    __asm__ volatile("s_waitcnt lgkmcnt(0)" : : : "memory");   // every read of the wavefront has returned
+    rec[2 * i + 1] = mi;
+    if (lane == 0) rec[1] = o.end0a * mi + o.end0b * mi2;
+    if (lane == DL_FIR_PAD) rec[2 * (n - 1) + 1] = o.end1a * mi + o.end1b * mi2;
+}
+#endif
+
+// Moment form, abscissa in units of the knot spacing: on interval j with u = t - j,
+//   S = y_j + u [(y_j+1 - y_j) - (2 m_j + m_j+1) + u (3 m_j + u (m_j+1 - m_j))],   m = M h^2 / 6
+// -- the cubic of dl_fs_phase2d_toep on the exactly uniform grid (no dlt shift), continued the same way under extrapolation.  The four operands are 32 contiguous
+// bytes at 16 j: two 16-byte LDS reads from one address, consecutive lanes on consecutive 16-byte slots.
+DL_HD double dl_spline_eval_m(const DlObsDev& o, const DlFsShared& s, double t) {
+    int j = (int)t;
+#if defined(__HIP_DEVICE_COMPILE__)
+    __asm__("v_med3_i32 %0, %1, 0, %2" : "=v"(j) : "v"(j), "s"(o.n_t - 2));
+#else
+    j = j < 0 ? 0 : j;
+    if (j > o.n_t - 2) j = o.n_t - 2;
+#endif
+    const double u = t - (double)j;
+    const double* r = s.coef + 2 * j;
+    const double y0 = r[0], m0 = r[1], y1 = r[2], m1 = r[3];
+    const double c1 = (y1 - y0) - fma(2., m0, m1);
+    return fma(u, fma(u, fma(u, m1 - m0, 3. * m0), c1), y0);
 }
 
 // interval index j and local coordinate u of abscissa x (log10 k'); extrapolation continues the end pieces like
@@ -703,8 +791,10 @@ DL_HD void dl_fs_phase3(int tid, int nthr, const DlObsDev& o, const DlFsShared& 
 // FAST variant of phase 3 that walks TWO wavenumbers (i, i + nthr) per pass of the mu loop: the per-mu shifts and fused weights are read from LDS
 // once for both (phase 3 is bound by LDS bandwidth: 32 B of interval coefficients + ~40 B of weights per evaluation), and eight independent
 // evaluation chains are in flight.  Same arithmetic, in the same order, per wavenumber as dl_fs_phase3<true, NL, EFT>.
-template <int NL, bool EFT>
-DL_HD void dl_fs_phase3_pair(int tid, int nthr, const DlObsDev& o, const DlFsShared& s, const double* lk_pref = nullptr) {
+// MOM: the spline in moment form (dl_spline_eval_m); power_row != nullptr (MOM only): every thread stores its own multipoles to the row (lanes i = tid .. of one
+// multipole: 512 contiguous bytes per wave-instruction) -- no output tile, no barrier, no dl_fs_phase4.
+template <int NL, bool EFT, bool MOM = false>
+DL_HD void dl_fs_phase3_pair(int tid, int nthr, const DlObsDev& o, const DlFsShared& s, const double* lk_pref = nullptr, double* power_row = nullptr) {
     const double qper = s.pt[DL_PT_QPER], sn0nd = s.pt[DL_PT_SN0ND];
     const bool damp = s.pt[DL_PT_DAMP] != 0.;
     const bool need_dd0 = EFT && o.n_ct > 0;
@@ -725,7 +815,8 @@ DL_HD void dl_fs_phase3_pair(int tid, int nthr, const DlObsDev& o, const DlFsSha
                     for (int c = 0; c < o.n_sn; ++c) acc += o.sn_matrix[((size_t)l * n_kin + i) * o.n_sn + c] * s.pt[DL_PT_SN + c];
                     pl += acc;
                 }
-                s.out[(size_t)l * n_kin + i] = pl;
+                if (MOM && power_row != nullptr) DL_STREAM_STORE(&power_row[(size_t)l * n_kin + i], pl);
+                else s.out[(size_t)l * n_kin + i] = pl;
             }
         }
         if (EFT && o.n_var > 0) s.out[o.n_in + i] = dd0;   // needed by the derivative rows (phase 4)
@@ -748,10 +839,10 @@ DL_HD void dl_fs_phase3_pair(int tid, int nthr, const DlObsDev& o, const DlFsSha
 #pragma unroll
             for (int q = 0; q < 4; ++q) lq[q] = s.pt[DL_PT_LQH + m0 + q];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) TA[q] = dl_spline_eval_t(o, s, lkA + lq[q]);
+            for (int q = 0; q < 4; ++q) TA[q] = MOM ? dl_spline_eval_m(o, s, lkA + lq[q]) : dl_spline_eval_t(o, s, lkA + lq[q]);
             if (two) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) TB[q] = dl_spline_eval_t(o, s, lkB + lq[q]);
+                for (int q = 0; q < 4; ++q) TB[q] = MOM ? dl_spline_eval_m(o, s, lkB + lq[q]) : dl_spline_eval_t(o, s, lkB + lq[q]);
             } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) TB[q] = 0.;

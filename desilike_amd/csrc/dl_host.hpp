@@ -63,7 +63,7 @@ struct DlObsHost {
     std::vector<double> bias;     // [n_out]: W . (sn_in (x) 1) + offset[mask] - sn_out        (window.py:459-473)
     std::vector<double> flatdata; // [n_out]
     size_t off_kin, off_lkin, off_mu, off_wmu, off_xt, off_pk, off_th, off_lg, off_ih, off_dlt, off_A, off_nC, off_inv, off_gf, off_gb, off_coef, off_ct, off_sn;
-    size_t off_cw, off_cn, off_pknowk, off_ml, off_pass, off_png = 0, off_band = 0;
+    size_t off_cw, off_cn, off_pknowk, off_ml, off_pass, off_png = 0, off_band = 0, off_krec = 0;
     size_t off_eng[3][6];   // xlo, xinv, weights, center, powers, coef of each emulator engine
     size_t off_stk[3] = {0, 0, 0};   // group table, amplitude table, fragment-ordered weights of the stacked table engine
     int marg_vp[DL_N_VPARS];
@@ -74,7 +74,7 @@ struct DlObsHost {
         dev.kin = base + off_kin; dev.lkin = base + off_lkin; dev.mu = base + off_mu; dev.wmu = base + off_wmu;
         dev.x_t = base + off_xt; dev.pk_fid = base + off_pk; dev.sf_th = base + off_th; dev.sf_lg = base + off_lg;
         dev.ih = base + off_ih; dev.dlt = base + off_dlt; dev.sp_A = base + off_A; dev.sp_nC = base + off_nC; dev.sp_inv = base + off_inv;
-        dev.sp_gf = base + off_gf; dev.sp_gb = base + off_gb; dev.coef_fixed = base + off_coef;
+        dev.sp_gf = base + off_gf; dev.sp_gb = base + off_gb; dev.coef_fixed = base + off_coef; dev.knot_rec = base + off_krec;
         dev.ct_matrix = base + off_ct; dev.sn_matrix = base + off_sn;
         dev.coef_w = base + off_cw; dev.coef_n = base + off_cn; dev.pknow_k = base + off_pknowk; dev.ml_tab = base + off_ml; dev.pass_tab = base + off_pass; dev.png_alpha = base + off_png; dev.band_tab = base + off_band;
         for (int e = 0; e < 3; ++e) {
@@ -500,6 +500,30 @@ inline bool dl_build_obs(const dl_config& cfg, int iobs, int n_params, DlObsHost
     d.toeplitz = (d.uniform_knots && d.n_t >= 4 * DL_FIR_PAD && !getenv("DL_NO_TOEPLITZ")) ? 1 : 0;
     for (int j = 0; j + 1 < d.n_t && d.toeplitz; ++j)
         if (std::fabs((x_t[j + 1] - x_t[j]) * d.inv_hx - 1.) > 1e-11) d.toeplitz = 0;
+    // Moment form of the fast kernels (dl_spline_eval_m): the spline is evaluated on the exactly uniform grid, without the per-interval shift dlt.  Evaluating at t
+    // instead of t + dlt_j inv_hx changes the value by |dS/dt| dlt_j inv_hx, relative to S by g dlt_j inv_hx with g = |dlnS/dt| the logarithmic change of the table per
+    // knot spacing: g is bounded here by the largest |ln(pk[j+1] / pk[j])| of the fiducial table plus what the template's shape parameters can add per spacing
+    // (exp(dm / a tanh(a ln k/kp) + dn ln k/kp): slope at most |dm| + |dn| in ln k -- 3.5 at the ends of the ShapeFit priors, taken as 4 -- times ln(10) / inv_hx).
+    // Selected only where g max|dlt| inv_hx < 1e-14.
+    d.moment_form = 0;
+    std::vector<double> knot_rec(2, 0.);
+    if (d.toeplitz && !d.fixed_spline && d.templ == 1) {   // (the bound on g below is the ShapeFit template's)
+        double g = 4. * std::log(10.) / d.inv_hx, dmax = 0.;
+        double gfid = 0.;
+        for (int j = 0; j + 1 < d.n_t; ++j) {
+            const double r = (pk[j] > 0. && pk[j + 1] > 0.) ? std::fabs(std::log(pk[j + 1] / pk[j])) : HUGE_VAL;
+            if (!(r <= gfid)) gfid = r;
+        }
+        g += gfid;
+        for (int j = 0; j < d.n_t; ++j) dmax = std::max(dmax, std::fabs(dlt[j] * d.inv_hx));
+        if (g * dmax < 1e-14) d.moment_form = 1;
+        if (d.moment_form && d.dn.col < 0) {
+            // dn is a constant input: its factor of the template is folded into the table; one 16-byte record per knot
+            knot_rec.resize((size_t)2 * d.n_t);
+            for (int j = 0; j < d.n_t; ++j) { knot_rec[2 * j] = pk[j] * std::exp(d.dn.value * sf_lg[j]); knot_rec[2 * j + 1] = sf_th[j]; }
+            d.moment_form |= 2;
+        }
+    }
     // segmented sweeps: 64 segments, the state entering each is a dot product with products of the multipliers
     int m = d.n_t - 2;
     d.seg_warm = sp.warm;
@@ -619,7 +643,7 @@ inline bool dl_build_obs(const dl_config& cfg, int iobs, int n_params, DlObsHost
     oh.off_kin = arena.push(kin); oh.off_lkin = arena.push(lkin); oh.off_mu = arena.push(mu); oh.off_wmu = arena.push(wmu);
     oh.off_xt = arena.push(x_t); oh.off_pk = arena.push(pk); oh.off_th = arena.push(sf_th); oh.off_lg = arena.push(sf_lg);
     oh.off_ih = arena.push(sp.ih); oh.off_dlt = arena.push(dlt); oh.off_A = arena.push(sp.A); oh.off_nC = arena.push(sp.nC); oh.off_inv = arena.push(sp.inv);
-    oh.off_gf = arena.push(gf); oh.off_gb = arena.push(gb); oh.off_coef = arena.push(coef);
+    oh.off_gf = arena.push(gf); oh.off_gb = arena.push(gb); oh.off_coef = arena.push(coef); oh.off_krec = arena.push(knot_rec);
     oh.off_ct = arena.push(ctm); oh.off_sn = arena.push(snm);
     oh.off_cw = arena.push(coef_w); oh.off_cn = arena.push(coef_n); oh.off_pknowk = arena.push(pknow_k);
     std::vector<double> png_alpha(2, 0.);

@@ -27,6 +27,8 @@ struct DlOptions {
                                         // 1 networks of the next batch under the feature GEMM (+2: without raised priority), 4 the two halves of the workgroup on half of the networks each
     bool ens_global, ens_force_comm, ens_no_defer, ens_no_fold, ens_stamps, ens_fold_stamps;
     bool no_emu_fused, no_gram_epilogue, step_kernel, chi2_fused, no_chi2_big;   // DL_NO_EMU_FUSED, DL_NO_GRAM_EPILOGUE, DL_STEP_KERNEL, DL_CHI2_FUSED, DL_NO_CHI2_BIG (dl_api.hip)
+    bool fs_no_moments;   // DL_FS_NO_MOMENTS=1: the fast theory kernels on their interval-polynomial path (polynomial stage, output tile, knot loop without prefetch) where
+                          // the moment form would apply (DlObsDev::moment_form; A/B measurements and the parity test of the two paths)
     int xcd_local;    // DL_XCD_LOCAL: 0 off, 1 chi2 GEMM path (default), 2 also the theory kernel's point order
     long long chi2_max_rows;   // DL_CHI2_GEMM_MAX (default 2048): above, the split-K / LDS-DMA GEMM paths
     int cg_mt;        // DL_CG_MT: forced row tile of the chi2 GEMM (0: chosen per batch)
@@ -42,7 +44,8 @@ const DlOptions& dl_options();
 // obs_host: HOST array of observables whose pointers already point into device memory (passed by value to the kernel)
 void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* theta, int n_params, int64_t B, double* power, int64_t ld_power, double* tables,
                          int64_t ld_tables, hipStream_t stream, double* feat = nullptr, int64_t feat_ld = 0, int xcd_block = 0,   // xcd_block: rows per row block of the consuming GEMM (0: points in launch order)
-                         const DlObsDev* obs_dev = nullptr);   // obs_dev: the same observables as a DEVICE array (enables one launch for all of them)
+                         const DlObsDev* obs_dev = nullptr,    // obs_dev: the same observables as a DEVICE array (enables one launch for all of them)
+                         bool moments = true);                 // moments = false: never the moment form (the gradient entry point: value and gradient from the same interval polynomials)
 // bias is added to rows r with r % bias_period == 0 only (bias_period = 1: every row)
 void dl_launch_window_gemm(const double* A, int64_t lda, const double* Wt, int64_t ldw, const double* bias, double* C, int64_t ldc, int64_t M, int N_valid, int N_pad,
                            int K_pad, int bias_period, hipStream_t stream);

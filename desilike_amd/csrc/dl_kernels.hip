@@ -64,6 +64,7 @@ static void dl_options_read() {
     o.host_mode = std::getenv("DL_HOST_MODE") ? atoi(std::getenv("DL_HOST_MODE")) : -1;
     auto flag = [](const char* name) { const char* v = std::getenv(name); return v != nullptr && atoi(v) != 0; };
     o.no_emu_fused = on("DL_NO_EMU_FUSED"); o.no_gram_epilogue = on("DL_NO_GRAM_EPILOGUE"); o.no_chi2_big = on("DL_NO_CHI2_BIG");
+    o.fs_no_moments = flag("DL_FS_NO_MOMENTS");
     o.step_kernel = flag("DL_STEP_KERNEL"); o.chi2_fused = flag("DL_CHI2_FUSED"); o.chi2_bfrag = flag("DL_CHI2_BFRAG");
     o.xcd_local = std::getenv("DL_XCD_LOCAL") ? atoi(std::getenv("DL_XCD_LOCAL")) : 1;
     o.chi2_max_rows = std::getenv("DL_CHI2_GEMM_MAX") ? atoll(std::getenv("DL_CHI2_GEMM_MAX")) : 2048;
@@ -80,7 +81,10 @@ __device__ __forceinline__ int dl_fs_point_of_wg(int wg, int xblk) { return xblk
 // SUB: the point is evaluated by a 256-thread SUB-GROUP of a larger workgroup (dl_step_kernel: four points per 1024-thread workgroup): `lds_sub`, `tid_sub`, `b_sub` name its
 // share of LDS, the thread's index in the sub-group and the point; every sub-group runs the same sequence of barriers (the branches between them are uniform in the observable).
 // NT: threads of the point's workgroup (DL_FS_THREADS; the wide form of small batches, dl_fullshape_wide_kernel, runs a point on 512: every phase strides by the thread count)
-template <bool FAST, int NL, bool EFT, bool DENSE, bool TH_ROW = false, bool SUB = false, int NT = DL_FS_THREADS>
+// MOM (FAST, no counter terms, not DENSE; launched only for observables with DlObsDev::moment_form): the spline is evaluated from (knot value, moment) records -- the
+// interval-polynomial stage shrinks to the end fix-up of one wavefront, the knot records of every round are requested at the top, and rows without pass-through columns
+// or derivative rows are stored by the evaluating threads themselves (no output tile, no last barrier).
+template <bool FAST, int NL, bool EFT, bool DENSE, bool TH_ROW = false, bool SUB = false, int NT = DL_FS_THREADS, bool MOM = false>
 __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const double* __restrict__ theta, int n_params, double* __restrict__ power,
                                                   int64_t ld_power, double* __restrict__ tables, int64_t ld_tables, int stop_after, unsigned long long* __restrict__ stamps,
                                                   const double* th_row = nullptr,     // th_row: the point's parameters already in LDS (dl_fullshape_ens_kernel)
@@ -98,7 +102,9 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
     if (stamps != nullptr && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memrealtime();   // 100 MHz, same on every XCD
     // FAST instantiations are only launched when the convolution path applies (or the spline is fixed): the segmented sweeps are not compiled in
     const bool toep = !o.fixed_spline && (FAST || o.toeplitz);
-    const DlFsShared s = dl_fs_shared_carve(lds, o.n_t, o.n_in, dl_fs_n_dd0(o), toep);
+    static_assert(!MOM || (FAST && !EFT && !DENSE), "the moment form belongs to the pair evaluation");
+    const DlFsShared s = MOM ? dl_fs_shared_carve_mom(lds, o) : dl_fs_shared_carve(lds, o.n_t, o.n_in, dl_fs_n_dd0(o), toep);
+    const bool direct = MOM && dl_fs_mom_direct(o);
     const double* th = TH_ROW ? th_row : theta + (size_t)b * n_params;
     const int tid = SUB ? tid_sub : (int)threadIdx.x, nthr = NT;
     if (stop_after == -1) return;  // stop_after != 0: timing diagnostics only (DL_FS_STOP), outputs are then incomplete
@@ -116,8 +122,18 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
         DlMuCarry c;
         double dlt_pref[DL_TOEP_PREF];
 #pragma unroll
-        for (int it = 0; it < DL_TOEP_PREF; ++it) dlt_pref[it] = (toep && !mu_wave && tid + it * KT < o.n_t - 1) ? o.dlt[tid + it * KT] : 0.;
+        for (int it = 0; it < DL_TOEP_PREF; ++it) dlt_pref[it] = (!MOM && toep && !mu_wave && tid + it * KT < o.n_t - 1) ? o.dlt[tid + it * KT] : 0.;
+        // moment form: the knot records of all rounds (the mu wave builds no knots)
+        const bool knot_rec = MOM && (o.moment_form & 2);
+        double kr[DL_KNOT_PREF][2];
+#pragma unroll
+        for (int it = 0; it < DL_KNOT_PREF; ++it) {
+            const bool live = knot_rec && !mu_wave && tid + it * KT < o.n_t;
+            const double2 r = live ? *reinterpret_cast<const double2*>(o.knot_rec + 2 * (size_t)(tid + it * KT)) : make_double2(0., 0.);   // (the arena keeps every array 16-byte aligned)
+            kr[it][0] = r.x; kr[it][1] = r.y;
+        }
         if (mu_wave) dl_fs_mu_partA(o, th, mu_lane ? m : 0, c);
+        else if (knot_rec) dl_fs_knots_rec(tid, KT, o, th, s, kr);
         else dl_fs_knots(tid, KT, o, th, s);
         if (o.fixed_spline && mu_wave) {
             dl_fs_mu_partB(c);
@@ -129,14 +145,15 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
         if (stop_after == 1) return;
         if (toep) {
             if (mu_wave) dl_fs_mu_partB(c);
-            else dl_fs_phase2_fir(tid, KT, o, s);
+            else dl_fs_phase2_fir<MOM>(tid, KT, o, s);
             __syncthreads();
             DL_STAMP(2)
             if (stop_after == 2) return;
             if (mu_wave) {
                 if (mu_lane) dl_fs_mu_partC(o, s, m, c, false);
                 if (scalar_lane) dl_fs_scalars(o, th, s, c, false);
-            } else dl_fs_phase2d_toep(tid, KT, o, s, dlt_pref);
+            } else if (MOM) { if (tid < 64) dl_fs_mom_fixup(tid, o, s); }
+            else dl_fs_phase2d_toep(tid, KT, o, s, dlt_pref);
             __syncthreads();
             DL_STAMP(3)
             if (stop_after == 5) return;
@@ -176,31 +193,44 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
     }
     double* prow = power + (size_t)b * (1 + o.n_var) * ld_power + o.col_offset;
     double* trow = tables ? tables + (size_t)b * ld_tables : nullptr;
-    if (FAST && !EFT && !DENSE) dl_fs_phase3_pair<NL, EFT>(tid, nthr, o, s, lk_pref);   // (with counter terms the pair variant spills registers)
+    if (FAST && !EFT && !DENSE) dl_fs_phase3_pair<NL, EFT, MOM>(tid, nthr, o, s, lk_pref, direct ? prow : nullptr);   // (with counter terms the pair variant spills registers)
     else dl_fs_phase3<FAST, NL, EFT>(tid, nthr, o, s, trow, lk_pref);
-    __syncthreads();
-    DL_STAMP(4)
-    dl_fs_phase4(tid, nthr, o, s, th, prow, ld_power);
+    if (!direct) {
+        __syncthreads();
+        DL_STAMP(4)
+        dl_fs_phase4(tid, nthr, o, s, th, prow, ld_power);
+    } else {
+        DL_STAMP(4)   // (thread 0's own evaluation and stores: no barrier on this path, the stamp is not the workgroup's)
+    }
     DL_STAMP(5)
     if (stamps != nullptr && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memrealtime();
 #undef DL_STAMP
 }
 
-template <bool FAST, int NL, bool EFT, bool DENSE = false>
+template <bool FAST, int NL, bool EFT, bool DENSE = false, bool MOM = false>
 __global__ __launch_bounds__(DL_FS_THREADS, DENSE ? 5 : 4) void dl_fullshape_kernel(const DlObsDev o, const double* __restrict__ theta, int n_params, double* __restrict__ power,
                                                                      int64_t ld_power, double* __restrict__ tables, int64_t ld_tables, int stop_after, unsigned long long* __restrict__ stamps) {
     dl_obs_prefetch((const void*)__builtin_amdgcn_kernarg_segment_ptr());
-    dl_fullshape_body<FAST, NL, EFT, DENSE>(o, theta, n_params, power, ld_power, tables, ld_tables, stop_after, stamps);
+    dl_fullshape_body<FAST, NL, EFT, DENSE, false, false, DL_FS_THREADS, MOM>(o, theta, n_params, power, ld_power, tables, ld_tables, stop_after, stamps);
 }
+
+// The moment form applies (kernels of one launch share it: every observable must qualify); DL_FS_NO_MOMENTS selects the interval-polynomial path everywhere
+static bool dl_fs_use_moments(const DlObsDev* obs_host, int n_obs) {
+    if (dl_options().fs_no_moments) return false;
+    for (int i = 0; i < n_obs; ++i)
+        if (!(obs_host[i].moment_form & 1) || obs_host[i].n_ct > 0 || obs_host[i].n_sn > 0) return false;
+    return true;
+}
+static size_t dl_fs_fast_shared_bytes(const DlObsDev& oh, bool mom) { return (mom ? dl_fs_mom_shared_doubles(oh) : dl_fs_shared_doubles_obs(oh, true)) * sizeof(double); }
 
 // Small batches (B x observables <= 256: at most one 256-thread workgroup per CU, a chain of latencies on a quarter of the CU's wave slots): the same body on 512 threads per point --
 // seven waves build the spline (knots and interval polynomials stride by the thread count), the evaluation phase holds ONE wavenumber per thread instead of two.  Measured (round 6,
 // profiles/r06d_wide_theory.txt): 64 - 256 points 18.0 - 18.2 -> 17.3 - 17.6 us per step; 512 points 19.05 -> 19.2, 1024 points 23.6 -> 28.6 us (four 512-thread workgroups do not fit a CU).
-template <int NL>
+template <int NL, bool MOM = false>
 __global__ __launch_bounds__(512, 2) void dl_fullshape_wide_kernel(const DlObsDev o, const double* __restrict__ theta, int n_params, double* __restrict__ power,
                                                                  int64_t ld_power, int stop_after, unsigned long long* __restrict__ stamps) {
     dl_obs_prefetch((const void*)__builtin_amdgcn_kernarg_segment_ptr());
-    dl_fullshape_body<true, NL, false, false, false, false, 512>(o, theta, n_params, power, ld_power, nullptr, 0, stop_after, stamps);
+    dl_fullshape_body<true, NL, false, false, false, false, 512, MOM>(o, theta, n_params, power, ld_power, nullptr, 0, stop_after, stamps);
 }
 
 // ---- scale-dependent bias from local primordial non-Gaussianity (theory kind 5; primordial_non_gaussianity.py:75-112) ---------------------------------------------
@@ -256,10 +286,10 @@ __global__ __launch_bounds__(DL_FS_THREADS, 2) void dl_png_kernel(DlObsDev o, co
 // Several observables in ONE launch (blockIdx.y = observable): two DlObsDev (2 x 2016 bytes) do not fit the 4 KB kernarg segment, so the structs are read from a
 // device array -- uniform, read-only addresses: scalar loads all the same.  Saves one launch ramp / drain per extra observable where the step is launch-latency
 // bound (two tracers x 256 walkers: 2 x 8.6 us -> one launch).
-template <bool FAST, int NL, bool EFT, bool DENSE = false>
+template <bool FAST, int NL, bool EFT, bool DENSE = false, bool MOM = false>
 __global__ __launch_bounds__(DL_FS_THREADS, DENSE ? 5 : 4) void dl_fullshape_multi_kernel(const DlObsDev* __restrict__ obs, const double* __restrict__ theta, int n_params,
                                                                            double* __restrict__ power, int64_t ld_power, int stop_after) {
-    dl_fullshape_body<FAST, NL, EFT, DENSE>(obs[blockIdx.y], theta, n_params, power, ld_power, nullptr, 0, stop_after, nullptr);
+    dl_fullshape_body<FAST, NL, EFT, DENSE, false, false, DL_FS_THREADS, MOM>(obs[blockIdx.y], theta, n_params, power, ld_power, nullptr, 0, stop_after, nullptr);
 }
 
 // ---- folded ensemble update (dl_ens_fold.h): the workgroup derives the proposal it evaluates --------------------------------------------------------------------
@@ -340,7 +370,7 @@ __device__ __forceinline__ void dl_ens_write_state(const DlEnsFold& f, int e, do
 
 // (non-DENSE: three workgroups per CU instead of four -- 168 registers: the prologue's values and the two-wavenumber projection loop do not fit 128 without spills,
 //  and a half-ensemble of a few hundred proposals does not fill four slots per CU anyway)
-template <int NL, bool DENSE = false>
+template <int NL, bool DENSE = false, bool MOM = false>
 __global__ __launch_bounds__(DL_FS_THREADS, DENSE ? 5 : 3) void dl_fullshape_ens_kernel(const DlObsDev* __restrict__ obs, const DlEnsFold f, double* __restrict__ power, int64_t ld_power,
                                                                          int flags, int B) {
     __shared__ double dl_ens_theta[DL_ENS_MAXP];
@@ -359,7 +389,7 @@ __global__ __launch_bounds__(DL_FS_THREADS, DENSE ? 5 : 3) void dl_fullshape_ens
     }
     __syncthreads();
     if (f.stamps != nullptr && blockIdx.y == 0 && threadIdx.x == 0) { f.stamps[(size_t)dl_fs_point_of_wg(blockIdx.x, (flags >> 8) & 0xff) * 8 + 0] = t_entry; f.stamps[(size_t)dl_fs_point_of_wg(blockIdx.x, (flags >> 8) & 0xff) * 8 + 5] = __builtin_amdgcn_s_memtime(); }
-    dl_fullshape_body<true, NL, false, DENSE, true>(obs[blockIdx.y], nullptr, f.P, power, ld_power, nullptr, 0, flags, nullptr, dl_ens_theta);
+    dl_fullshape_body<true, NL, false, DENSE, true, false, DL_FS_THREADS, MOM>(obs[blockIdx.y], nullptr, f.P, power, ld_power, nullptr, 0, flags, nullptr, dl_ens_theta);
     if (f.stamps != nullptr && blockIdx.y == 0 && threadIdx.x == 0) f.stamps[(size_t)dl_fs_point_of_wg(blockIdx.x, (flags >> 8) & 0xff) * 8 + 6] = __builtin_amdgcn_s_memtime();
 }
 
@@ -372,17 +402,18 @@ bool dl_launch_fullshape_ens(const DlObsDev* obs_host, int n_obs, const DlObsDev
         const DlObsDev& oh = obs_host[i];
         const bool generic = !oh.uniform_knots || !(oh.toeplitz || oh.fixed_spline);
         if (oh.theory >= 2 || generic || oh.n_ct > 0 || oh.n_sn > 0 || (oh.n_ell <= 3) != nl3) return false;
-        shmem = std::max(shmem, dl_fs_shared_doubles_obs(oh, true) * sizeof(double));
     }
     static const int64_t dense_min = getenv("DL_FS_DENSE_MIN") ? atoll(getenv("DL_FS_DENSE_MIN")) : 4096;
+    const bool dense = B * n_obs > dense_min, mom = !dense && dl_fs_use_moments(obs_host, n_obs);
+    for (int i = 0; i < n_obs; ++i) shmem = std::max(shmem, dl_fs_fast_shared_bytes(obs_host[i], mom));
     auto launch = [&](auto kernel) {
         if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
         const int flags = (xcd_block > 0 && B % (8 * xcd_block) == 0) ? (xcd_block << 8) : 0;
         const int n_extra = f.pend.half >= 0 ? (int)((B + DL_ENS_SLOTS_PER_WG - 1) / DL_ENS_SLOTS_PER_WG) : 0;   // workgroups that write the state after the pending accepts
         DL_LAUNCH(kernel, dim3((unsigned)(B + n_extra), (unsigned)n_obs), dim3(DL_FS_THREADS), shmem, stream, obs_dev, f, power, ld_power, flags, (int)B);
     };
-    if (nl3) { if (B * n_obs > dense_min) launch(dl_fullshape_ens_kernel<3, true>); else launch(dl_fullshape_ens_kernel<3>); }
-    else { if (B * n_obs > dense_min) launch(dl_fullshape_ens_kernel<5, true>); else launch(dl_fullshape_ens_kernel<5>); }
+    if (nl3) { if (dense) launch(dl_fullshape_ens_kernel<3, true>); else if (mom) launch(dl_fullshape_ens_kernel<3, false, true>); else launch(dl_fullshape_ens_kernel<3>); }
+    else { if (dense) launch(dl_fullshape_ens_kernel<5, true>); else if (mom) launch(dl_fullshape_ens_kernel<5, false, true>); else launch(dl_fullshape_ens_kernel<5>); }
     return true;
 }
 
@@ -600,7 +631,7 @@ __global__ __launch_bounds__(DL_FS_THREADS) void dl_emulated_kernel(const DlObsD
 }
 
 void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* theta, int n_params, int64_t B, double* power, int64_t ld_power, double* tables,
-                         int64_t ld_tables, hipStream_t stream, double* feat, int64_t feat_ld, int xcd_block, const DlObsDev* obs_dev) {
+                         int64_t ld_tables, hipStream_t stream, double* feat, int64_t feat_ld, int xcd_block, const DlObsDev* obs_dev, bool moments) {
     static const int stop_after = getenv("DL_FS_STOP") ? atoi(getenv("DL_FS_STOP")) : 0;   // per-phase timing diagnostics
     // DL_FS_STAMPS=<file>: in-kernel timestamps of the launches with B >= 256 are appended to <file> as text (synchronises: diagnostics only)
     static const char* stamp_file = getenv("DL_FS_STAMPS");
@@ -618,17 +649,18 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
             const DlObsDev& oh = obs_host[i];
             const bool generic = !oh.uniform_knots || !(oh.toeplitz || oh.fixed_spline);
             if (oh.theory >= 2 || generic || (oh.n_ct > 0 || oh.n_sn > 0) != eft0 || (oh.n_ell <= 3) != nl3) same = false;
-            shmem = std::max(shmem, dl_fs_shared_doubles_obs(oh, true) * sizeof(double));
         }
         if (same && !eft0) {
             static const int64_t dense_min = getenv("DL_FS_DENSE_MIN") ? atoll(getenv("DL_FS_DENSE_MIN")) : 4096;
+            const bool dense = B * n_obs > dense_min, mom = moments && !dense && dl_fs_use_moments(obs_host, n_obs);
+            for (int i = 0; i < n_obs; ++i) shmem = std::max(shmem, dl_fs_fast_shared_bytes(obs_host[i], mom));
             auto launch = [&](auto kernel) {
                 if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
                 const int flags = (xcd_block > 0 && B % (8 * xcd_block) == 0) ? (xcd_block << 8) : 0;
                 DL_LAUNCH(kernel, dim3((unsigned)B, (unsigned)n_obs), dim3(DL_FS_THREADS), shmem, stream, obs_dev, theta, n_params, power, ld_power, flags);
             };
-            if (nl3) { if (B * n_obs > dense_min) launch(dl_fullshape_multi_kernel<true, 3, false, true>); else launch(dl_fullshape_multi_kernel<true, 3, false>); }
-            else { if (B * n_obs > dense_min) launch(dl_fullshape_multi_kernel<true, 5, false, true>); else launch(dl_fullshape_multi_kernel<true, 5, false>); }
+            if (nl3) { if (dense) launch(dl_fullshape_multi_kernel<true, 3, false, true>); else if (mom) launch(dl_fullshape_multi_kernel<true, 3, false, false, true>); else launch(dl_fullshape_multi_kernel<true, 3, false>); }
+            else { if (dense) launch(dl_fullshape_multi_kernel<true, 5, false, true>); else if (mom) launch(dl_fullshape_multi_kernel<true, 5, false, false, true>); else launch(dl_fullshape_multi_kernel<true, 5, false>); }
             return;
         }
     }
@@ -669,7 +701,12 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
         }
         const DlObsDev& oh = obs_host[i];
         const bool generic = tables || !oh.uniform_knots || !(oh.toeplitz || oh.fixed_spline);
-        size_t shmem = dl_fs_shared_doubles_obs(obs_host[i], !generic) * sizeof(double);
+        static const int64_t dense_min = getenv("DL_FS_DENSE_MIN") ? atoll(getenv("DL_FS_DENSE_MIN")) : 4096;   // batches above: the 5-workgroups-per-CU variant
+        bool nl3 = oh.n_ell <= 3, eft = oh.n_ct > 0 || oh.n_sn > 0;
+        static const int wide_env = getenv("DL_FS_WIDE") ? atoi(getenv("DL_FS_WIDE")) : -1;      // 1 / 0: force / forbid the 512-thread form (default: batches of at most 256 workgroups)
+        const bool wide = !generic && !eft && tables == nullptr && (wide_env == 1 || (wide_env != 0 && B * n_obs <= 256));
+        const bool mom = moments && !generic && !eft && (wide || B <= dense_min) && dl_fs_use_moments(&oh, 1);
+        size_t shmem = generic ? dl_fs_shared_doubles_obs(oh, false) * sizeof(double) : dl_fs_fast_shared_bytes(oh, mom);
         auto launch = [&](auto kernel) {
             if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);  // e.g. 2000-knot BAO tables
             const int flags = (xcd_block > 0 && stop_after == 0 && B % (8 * xcd_block) == 0) ? (xcd_block << 8) : stop_after;
@@ -685,21 +722,20 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
                 }
             }
         };
-        static const int64_t dense_min = getenv("DL_FS_DENSE_MIN") ? atoll(getenv("DL_FS_DENSE_MIN")) : 4096;   // batches above: the 5-workgroups-per-CU variant
-        bool nl3 = oh.n_ell <= 3, eft = oh.n_ct > 0 || oh.n_sn > 0;
-        static const int wide_env = getenv("DL_FS_WIDE") ? atoi(getenv("DL_FS_WIDE")) : -1;      // 1 / 0: force / forbid the 512-thread form (default: batches of at most 256 workgroups)
-        const bool wide = !generic && !eft && tables == nullptr && (wide_env == 1 || (wide_env != 0 && B * n_obs <= 256));
         if (wide) {
-            if (shmem > 48 * 1024) { (void)hipFuncSetAttribute((const void*)dl_fullshape_wide_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); (void)hipFuncSetAttribute((const void*)dl_fullshape_wide_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); }
-            const int flags = (xcd_block > 0 && stop_after == 0 && B % (8 * xcd_block) == 0) ? (xcd_block << 8) : stop_after;
-            if (nl3) DL_LAUNCH(dl_fullshape_wide_kernel<3>, dim3((unsigned)B), dim3(512), shmem, stream, obs_host[i], theta, n_params, power, ld_power, flags, stamps);
-            else DL_LAUNCH(dl_fullshape_wide_kernel<5>, dim3((unsigned)B), dim3(512), shmem, stream, obs_host[i], theta, n_params, power, ld_power, flags, stamps);
+            auto launch_wide = [&](auto kernel) {
+                if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+                const int flags = (xcd_block > 0 && stop_after == 0 && B % (8 * xcd_block) == 0) ? (xcd_block << 8) : stop_after;
+                DL_LAUNCH(kernel, dim3((unsigned)B), dim3(512), shmem, stream, obs_host[i], theta, n_params, power, ld_power, flags, stamps);
+            };
+            if (nl3) { if (mom) launch_wide(dl_fullshape_wide_kernel<3, true>); else launch_wide(dl_fullshape_wide_kernel<3>); }
+            else { if (mom) launch_wide(dl_fullshape_wide_kernel<5, true>); else launch_wide(dl_fullshape_wide_kernel<5>); }
             continue;
         }
         if (generic) launch(dl_fullshape_kernel<false, 5, true>);   // generic: run-time decisions
-        else if (nl3 && !eft) { if (B > dense_min) launch(dl_fullshape_kernel<true, 3, false, true>); else launch(dl_fullshape_kernel<true, 3, false>); }
+        else if (nl3 && !eft) { if (B > dense_min) launch(dl_fullshape_kernel<true, 3, false, true>); else if (mom) launch(dl_fullshape_kernel<true, 3, false, false, true>); else launch(dl_fullshape_kernel<true, 3, false>); }
         else if (nl3) launch(dl_fullshape_kernel<true, 3, true>);
-        else if (!eft) { if (B > dense_min) launch(dl_fullshape_kernel<true, 5, false, true>); else launch(dl_fullshape_kernel<true, 5, false>); }
+        else if (!eft) { if (B > dense_min) launch(dl_fullshape_kernel<true, 5, false, true>); else if (mom) launch(dl_fullshape_kernel<true, 5, false, false, true>); else launch(dl_fullshape_kernel<true, 5, false>); }
         else launch(dl_fullshape_kernel<true, 5, true>);
     }
 }

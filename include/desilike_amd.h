@@ -237,6 +237,8 @@ int  dl_profile_read(dl_ctx* ctx, double* ms, int32_t n);
  *     DL_FM_NO_STAGE, DL_NO_FEATURE_PATH, DL_NO_TOEPLITZ, DL_NO_PANEL_SKIP, DL_NO_ROW_ALIGN, DL_NO_CHI2_BIG, DL_CHI2_FUSED, DL_STEP_KERNEL, DL_CHI2_GEMM_MAX, DL_CG_MT, DL_XCD_LOCAL,
  *     DL_FS_DENSE_MIN, DL_GEMM_DMA, DL_GEMM_WGS, DL_BAO_THREADS, DL_FFTLOG_GENERIC, DL_TNS_W, DL_TNS_WAVEK, DL_ENS_GLOBAL, DL_ENS_NO_DEFER, DL_ENS_NO_FOLD, DL_ENS_FORCE_COMM,
  *     DL_MH_NO_DEFER, DL_HOST_MODE (0 - 4: how the *_host entry points wait, see dl_eval_batch_host)
+ *     DL_FS_NO_MOMENTS (the fast full-shape kernels on their interval-polynomial path where the moment form would apply: agrees with the default to rounding, ~1e-15 of a row's
+ *     largest value, not bit for bit -- tests/test_gpu_fullshape_moments.py compares the two)
  *   diagnostics (in-kernel time stamps written to the named file, per-phase early exits; they synchronise: never set in production):
  *     DL_FS_STAMPS, DL_FS_STOP, DL_CG_STAMPS, DL_EF_STAMPS, DL_FM_STAMPS, DL_STK_STAMPS, DL_STEP_STAMPS, DL_ENS_STAMPS, DL_ENS_FOLD_STAMPS
  *   environment of the collectives: DL_RCCL_PATH, DL_COMM_TIMEOUT (desilike_amd/parallel.py, bench.py) */

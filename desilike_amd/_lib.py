@@ -83,6 +83,18 @@ SYMBOLS = {
     'dl_mclmc_get_moments': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, ctypes.c_void_p]),
     'dl_mclmc_run': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_mclmc_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
+    'dl_smc_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_uint64, ctypes.c_double,
+                                     _c_double_p]),
+    'dl_smc_destroy': (None, [ctypes.c_void_p]),
+    'dl_smc_set_hyper': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    'dl_smc_set_particles': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_void_p]),
+    'dl_smc_set_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), _c_double_p, _c_double_p,
+                                        ctypes.c_void_p]),
+    'dl_smc_get_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), _c_double_p, _c_double_p,
+                                        ctypes.c_void_p]),
+    'dl_smc_get_decisions': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.c_void_p]),
+    'dl_smc_run': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_smc_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
     'dl_mlp_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int32, _c_int32_p, ctypes.c_int32, _c_double_p]),
     'dl_mlp_destroy': (None, [ctypes.c_void_p]),
     'dl_mlp_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
@@ -950,6 +962,92 @@ class DeviceMCLMC(object):
     def close(self):
         if getattr(self, '_handle', None):
             self._lib.dl_mclmc_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceSMC(object):
+    """Owner of one ``dl_smc`` (include/desilike_amd.h): ``nsystems`` independent systems of ``nparticles`` particles of tempered sequential Monte Carlo resident on the
+    GPU of ``ctx``; ``widths`` [P]: the width or scale of every parameter's prior."""
+
+    def __init__(self, ctx, nsystems, nparticles, widths, system_ids=None, seed=0, offset=0.):
+        lib = load()
+        if ctx.expand is not None:
+            raise NotImplementedError('the device-resident sampler moves in the columns of the device context: parameters derived by an expression need the host-driven sampler')
+        P = ctx.n_params
+        system_ids = np.ascontiguousarray(np.arange(nsystems) if system_ids is None else system_ids, dtype='i4')
+        if len(system_ids) != nsystems: raise ValueError('system_ids must have one entry per system')
+        widths = np.ascontiguousarray(widths, dtype='f8').reshape(P)
+        handle = ctypes.c_void_p()
+        if lib.dl_smc_create(ctypes.byref(handle), ctx._handle, int(nsystems), int(nparticles), system_ids.ctypes.data_as(_c_int32_p), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                             float(offset), _f64_ptr(widths)) != 0:
+            raise LibraryError(lib.dl_last_error(None).decode())
+        self._lib, self._handle, self._ctx = lib, handle, ctx     # (the context must outlive the sampler)
+        self.nsystems, self.nparticles, self.n_params, self.device, self.n_steps = int(nsystems), int(nparticles), P, ctx.device, 0
+
+    _check, _stream = DeviceNUTS._check, DeviceNUTS._stream
+
+    def info(self, key):
+        return int(self._lib.dl_smc_info(self._handle, key.encode()))
+
+    def set_hyper(self, ess_fraction, n_steps, target_acceptance, scale=1., stream=None):
+        self._check(self._lib.dl_smc_set_hyper(self._handle, float(ess_fraction), int(n_steps), float(target_acceptance), float(scale), self._stream(stream)))
+        self.n_steps = int(n_steps)
+
+    def set_particles(self, coords, stream=None):
+        coords = np.ascontiguousarray(coords, dtype='f8')
+        if coords.shape != (self.nsystems, self.nparticles, self.n_params):
+            raise ValueError('coords must have shape ({:d}, {:d}, {:d}), found {}'.format(self.nsystems, self.nparticles, self.n_params, coords.shape))
+        self._check(self._lib.dl_smc_set_particles(self._handle, _f64_ptr(coords), self._stream(stream)))
+
+    def _shapes(self):
+        K, N, P = self.nsystems, self.nparticles, self.n_params
+        return [(K, N, P), (K, N), (K, N), (K,), (K,), (K,), (K,), (K, P, P)]
+
+    def set_state(self, coords, loglike, logprior, beta, logz, counters, scale, factor, stream=None):
+        """What :meth:`get_state` returns."""
+        arrays = [np.ascontiguousarray(a, dtype='i8' if i == 5 else 'f8').reshape(shape) for i, (a, shape) in enumerate(zip([coords, loglike, logprior, beta, logz, counters, scale, factor],
+                                                                                                                      self._shapes()))]
+        args = [a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if i == 5 else _f64_ptr(a) for i, a in enumerate(arrays)]
+        self._check(self._lib.dl_smc_set_state(self._handle, *args, self._stream(stream)))
+
+    def get_state(self, stream=None):
+        """(coords [K, N, P], loglike [K, N], logprior [K, N], beta, logz (without the offset), counters, scale [K], factor [K, P, P]) as numpy arrays; synchronises."""
+        arrays = [np.empty(shape, dtype='i8' if i == 5 else 'f8') for i, shape in enumerate(self._shapes())]
+        args = [a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if i == 5 else _f64_ptr(a) for i, a in enumerate(arrays)]
+        self._check(self._lib.dl_smc_get_state(self._handle, *args, self._stream(stream)))
+        return tuple(arrays)
+
+    def get_decisions(self, stream=None):
+        """Of the last iteration: (ancestors [K, N], accept flags [K, n_steps, N], mean [K, P], covariance [K, P, P] lower triangle); synchronises."""
+        K, N, P = self.nsystems, self.nparticles, self.n_params
+        anc, flags, mean, cov = np.empty((K, N), dtype='i4'), np.empty((K, self.n_steps, N), dtype='u1'), np.empty((K, P)), np.empty((K, P, P))
+        self._check(self._lib.dl_smc_get_decisions(self._handle, anc.ctypes.data_as(ctypes.c_void_p), flags.ctypes.data_as(ctypes.c_void_p), _f64_ptr(mean), _f64_ptr(cov),
+                                                   self._stream(stream)))
+        return anc, flags.astype(bool), mean, np.tril(cov)
+
+    def buffers(self, quota):
+        """Record buffers of one batch: history [K, quota, 5], coords [K, quota, N, P], logposterior [K, quota, N], count [K, 2] (zeroed)."""
+        import torch
+        device = torch.device('cuda', self.device)
+        K, N, P = self.nsystems, self.nparticles, self.n_params
+        return (torch.zeros((K, quota, 5), dtype=torch.float64, device=device), torch.empty((K, quota, N, P), dtype=torch.float64, device=device),
+                torch.empty((K, quota, N), dtype=torch.float64, device=device), torch.zeros((K, 2), dtype=torch.int32, device=device))
+
+    def run(self, niterations, quota, buffers, stream=None):
+        """Enqueue ``niterations`` iterations of every system into the record ``buffers`` of a batch of ``quota`` records per system (asynchronous)."""
+        history, coords, logp, count = buffers
+        self._check(self._lib.dl_smc_run(self._handle, int(niterations), int(quota), ctypes.c_void_p(history.data_ptr()), ctypes.c_void_p(coords.data_ptr()),
+                                         ctypes.c_void_p(logp.data_ptr()), ctypes.c_void_p(count.data_ptr()), self._stream(stream)))
+
+    def close(self):
+        if getattr(self, '_handle', None):
+            self._lib.dl_smc_destroy(self._handle)
             self._handle = None
 
     def __del__(self):

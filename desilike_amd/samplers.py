@@ -1037,4 +1037,7 @@ def __getattr__(name):
     if name == 'MCLMCSampler':
         from . import mclmc
         return mclmc.MCLMCSampler
+    if name == 'SMCSampler':
+        from . import smc
+        return smc.SMCSampler
     raise AttributeError('module {!r} has no attribute {!r}'.format(__name__, name))

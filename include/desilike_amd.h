@@ -410,6 +410,48 @@ int  dl_mclmc_run(dl_mclmc* mclmc, int64_t nsteps, int32_t quota, int32_t thin_b
  * are in use), "dense", "adapt", "moments" */
 int64_t dl_mclmc_info(const dl_mclmc* mclmc, const char* key);
 
+/* ---- device-resident tempered sequential Monte Carlo with log-evidence --------------------------------------------------------------------------
+ * Adaptive tempered SMC (Del Moral, Doucet & Jasra 2006; the skeleton of the PocoMC the reference wraps in desilike/samplers/pocomc.py, with precondition=False,
+ * sample='rwm': none of its flows, preconditioned Crank-Nicolson or persistent reweighting) on ``nsystems`` independent systems of ``nparticles`` particles resident
+ * on the GPU (csrc/dl_smc.h states the algorithm, the order of every sum and the random draws).  The particles start from the prior at beta = 0; an iteration
+ * chooses the next inverse temperature by bisection on the effective sample size, adds to logZ, resamples systematically and mutates with ``n_steps`` random-walk
+ * Metropolis sweeps, each ONE dl_eval_batch over all nsystems x nparticles proposals; a system at beta = 1 keeps sweeping and records its particles.  The likelihood
+ * alone is tempered: log-likelihood and log-prior are kept apart (dl_eval_batch's loglike_dev / logprior_dev).  Nothing in dl_smc_run allocates or synchronises, and
+ * the host never reads beta to decide what to enqueue.  Errors: non-zero, message via dl_last_error(NULL). */
+typedef struct dl_smc dl_smc;
+/* nparticles: a multiple of 64 in 64 .. 16384; the context has 1 .. 64 parameters; system_ids[nsystems] global index of every system (NULL: 0 .. nsystems - 1; keys
+ * the draws); offset: the constant of a posterior context (added to the reported logZ and log-posteriors, never tempered); widths[P] (host): the width or scale of
+ * every parameter's prior, positive (the proposal's fallback for a component without variance) */
+int  dl_smc_create(dl_smc** out, dl_ctx* ctx, int32_t nsystems, int32_t nparticles, const int32_t* system_ids, uint64_t seed, double offset, const double* widths);
+void dl_smc_destroy(dl_smc* smc);
+/* ess_fraction in (0, 1), n_steps sweeps per iteration (1 .. 1024), target_acceptance in (0, 1), scale: the proposal scale of every system (replaces the adapted
+ * ones; 1e-3 .. 1e3); allocates where n_steps changes; synchronises */
+int  dl_smc_set_hyper(dl_smc* smc, double ess_fraction, int32_t n_steps, double target_acceptance, double scale, void* hip_stream);
+/* host coords[nsystems, nparticles, P]: evaluates log-likelihood and log-prior; an error if a log-prior is not finite (a particle outside the prior) or if no particle
+ * of a system has a finite log-likelihood (a particle without one has weight 0 from the first level on).  beta = 0, logZ = 0, counters = 0.  synchronises */
+int  dl_smc_set_particles(dl_smc* smc, const double* coords, void* hip_stream);
+/* host arrays, all required: coords[nsystems, nparticles, P], loglike and logprior [nsystems, nparticles], beta, logz (without the offset), counters, scale [nsystems],
+ * factor[nsystems, P, P] (the proposal's lower factor of the last level: a system at beta = 1 keeps it) -- what dl_smc_get_state returns: the run continues bit for
+ * bit.  synchronises */
+int  dl_smc_set_state(dl_smc* smc, const double* coords, const double* loglike, const double* logprior, const double* beta, const double* logz, const int64_t* counters,
+                      const double* scale, const double* factor, void* hip_stream);
+/* host arrays (any may be NULL), as dl_smc_set_state; synchronises */
+int  dl_smc_get_state(dl_smc* smc, double* coords, double* loglike, double* logprior, double* beta, double* logz, int64_t* counters, double* scale, double* factor,
+                      void* hip_stream);
+/* TEST AND DIAGNOSTIC ENTRY (no sampler needs it; tests/test_gpu_smc.py compares the device with the NumPy statement decision by decision through it): the discrete
+ * decisions and the moments of the LAST iteration, host arrays (any may be NULL): ancestors[nsystems, nparticles] (i for a system that did not resample),
+ * accepts[nsystems, n_steps, nparticles] (0 / 1), mean[nsystems, P], covariance[nsystems, P, P] (lower triangle; of the last level); synchronises */
+int  dl_smc_get_decisions(dl_smc* smc, int32_t* ancestors, uint8_t* accepts, double* mean, double* covariance, void* hip_stream);
+/* ``niterations`` iterations of every system, enqueued on ``hip_stream`` (asynchronous).  Every iteration of system k writes (beta, logZ + offset, ESS at the chosen
+ * step, mean acceptance of its sweeps, scale) into row count_dev[k, 0] of history_dev[nsystems, quota, 5]; an iteration that started at beta = 1 also writes its
+ * particles into slot count_dev[k, 1] of coords_dev[nsystems, quota, nparticles, P] and their log-likelihood + log-prior + offset into logp_dev[nsystems, quota,
+ * nparticles]; count_dev[nsystems, 2].  A system whose count_dev[k, 0] reached ``quota`` rests.  The counts are NOT reset: the caller zeroes them at the start of a
+ * batch (how the calls are chunked does not change the systems). */
+int  dl_smc_run(dl_smc* smc, int64_t niterations, int32_t quota, double* history_dev, double* coords_dev, double* logp_dev, int32_t* count_dev, void* hip_stream);
+/* integer properties: "nsystems", "nparticles", "n_params", "iterations" (enqueued since the particles were set), "evaluations" (rows given to dl_eval_batch),
+ * "n_steps" */
+int64_t dl_smc_info(const dl_smc* smc, const char* key);
+
 /* ---- MLP emulator training ---------------------------------------------------------------------------------------
  * The reference trains its MLP emulators through the third-party engine ``cosmoprimo.emulators.tools.MLPEmulatorEngine`` (desilike/emulators/__init__.py:510-533;
  * network structure: emulators/conversion.py:20-96).  Here: fp64 mini-batch Adam on the mean squared error of the (already scaled) outputs, entirely on the device

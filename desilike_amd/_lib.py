@@ -95,6 +95,19 @@ SYMBOLS = {
     'dl_smc_get_decisions': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.c_void_p]),
     'dl_smc_run': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_smc_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
+    'dl_nested_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_uint64, ctypes.c_double,
+                                        _c_double_p]),
+    'dl_nested_destroy': (None, [ctypes.c_void_p]),
+    'dl_nested_set_hyper': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    'dl_nested_set_live': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_void_p]),
+    'dl_nested_set_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), _c_double_p,
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p]),
+    'dl_nested_get_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), _c_double_p,
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p]),
+    'dl_nested_get_decisions': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.c_void_p]),
+    'dl_nested_run': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_nested_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
     'dl_mlp_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int32, _c_int32_p, ctypes.c_int32, _c_double_p]),
     'dl_mlp_destroy': (None, [ctypes.c_void_p]),
     'dl_mlp_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
@@ -1048,6 +1061,94 @@ class DeviceSMC(object):
     def close(self):
         if getattr(self, '_handle', None):
             self._lib.dl_smc_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceNested(object):
+    """Owner of one ``dl_nested`` (include/desilike_amd.h): ``nruns`` independent nested-sampling runs of ``nlive`` live points resident on the GPU of ``ctx``;
+    ``widths`` [P]: the width or scale of every parameter's prior."""
+    _dtypes = ['f8', 'f8', 'f8', 'f8', 'f8', 'i8', 'f8', 'i4']
+
+    def __init__(self, ctx, nruns, nlive, widths, run_ids=None, seed=0, offset=0.):
+        lib = load()
+        if ctx.expand is not None:
+            raise NotImplementedError('the device-resident sampler moves in the columns of the device context: parameters derived by an expression need the host-driven sampler')
+        P = ctx.n_params
+        run_ids = np.ascontiguousarray(np.arange(nruns) if run_ids is None else run_ids, dtype='i4')
+        if len(run_ids) != nruns: raise ValueError('run_ids must have one entry per run')
+        widths = np.ascontiguousarray(widths, dtype='f8').reshape(P)
+        handle = ctypes.c_void_p()
+        if lib.dl_nested_create(ctypes.byref(handle), ctx._handle, int(nruns), int(nlive), run_ids.ctypes.data_as(_c_int32_p), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                float(offset), _f64_ptr(widths)) != 0:
+            raise LibraryError(lib.dl_last_error(None).decode())
+        self._lib, self._handle, self._ctx = lib, handle, ctx     # (the context must outlive the sampler)
+        self.nruns, self.nlive, self.n_params, self.device, self.n_steps, self.ndelete = int(nruns), int(nlive), P, ctx.device, 0, 0
+
+    _check, _stream = DeviceNUTS._check, DeviceNUTS._stream
+
+    def info(self, key):
+        return int(self._lib.dl_nested_info(self._handle, key.encode()))
+
+    def set_hyper(self, ndelete, n_steps, target_acceptance, dlogz, scale=1., stream=None):
+        self._check(self._lib.dl_nested_set_hyper(self._handle, int(ndelete), int(n_steps), float(target_acceptance), float(dlogz), float(scale), self._stream(stream)))
+        self.ndelete, self.n_steps = int(ndelete), int(n_steps)
+
+    def set_live(self, coords, stream=None):
+        coords = np.ascontiguousarray(coords, dtype='f8')
+        if coords.shape != (self.nruns, self.nlive, self.n_params):
+            raise ValueError('coords must have shape ({:d}, {:d}, {:d}), found {}'.format(self.nruns, self.nlive, self.n_params, coords.shape))
+        self._check(self._lib.dl_nested_set_live(self._handle, _f64_ptr(coords), self._stream(stream)))
+
+    def _shapes(self):
+        K, N, P = self.nruns, self.nlive, self.n_params
+        return [(K, N, P), (K, N), (K, N), (K,), (K,), (K,), (K,), (K,)]
+
+    @staticmethod
+    def _pointer(a):
+        return a.ctypes.data_as(ctypes.POINTER({'i8': ctypes.c_int64, 'i4': ctypes.c_int32}[a.dtype.str[1:]])) if a.dtype.kind == 'i' else _f64_ptr(a)
+
+    def set_state(self, coords, loglike, logprior, logx, logz, counters, scale, modes, stream=None):
+        """What :meth:`get_state` returns."""
+        arrays = [np.ascontiguousarray(a, dtype=dtype).reshape(shape) for a, dtype, shape in zip([coords, loglike, logprior, logx, logz, counters, scale, modes], self._dtypes, self._shapes())]
+        self._check(self._lib.dl_nested_set_state(self._handle, *[self._pointer(a) for a in arrays], self._stream(stream)))
+
+    def get_state(self, stream=None):
+        """(coords [K, N, P], loglike [K, N], logprior [K, N], logx, logz (without the offset), counters, scale, modes [K]) as numpy arrays; synchronises."""
+        arrays = [np.empty(shape, dtype=dtype) for dtype, shape in zip(self._dtypes, self._shapes())]
+        self._check(self._lib.dl_nested_get_state(self._handle, *[self._pointer(a) for a in arrays], self._stream(stream)))
+        return tuple(arrays)
+
+    def get_decisions(self, stream=None):
+        """Of the last iteration: (ranks [K, N], seeds [K, M], accept flags [K, n_steps, M], mean [K, P], covariance [K, P, P] lower triangle); synchronises."""
+        K, N, P, M = self.nruns, self.nlive, self.n_params, self.ndelete
+        ranks, seeds, flags = np.empty((K, N), dtype='i4'), np.empty((K, M), dtype='i4'), np.empty((K, self.n_steps, M), dtype='u1')
+        mean, cov = np.empty((K, P)), np.empty((K, P, P))
+        self._check(self._lib.dl_nested_get_decisions(self._handle, ranks.ctypes.data_as(ctypes.c_void_p), seeds.ctypes.data_as(ctypes.c_void_p), flags.ctypes.data_as(ctypes.c_void_p),
+                                                      _f64_ptr(mean), _f64_ptr(cov), self._stream(stream)))
+        return ranks, seeds, flags.astype(bool), mean, np.tril(cov)
+
+    def buffers(self, quota):
+        """Record buffers of one batch: history [K, quota, 6], dead coords [K, quota, M, P], dead loglike, logprior, logweight [K, quota, M], count [K] (zeroed), modes [K]."""
+        import torch
+        device = torch.device('cuda', self.device)
+        K, M, P = self.nruns, self.ndelete, self.n_params
+        dead = [torch.empty((K, quota, M), dtype=torch.float64, device=device) for _ in range(3)]
+        return (torch.zeros((K, quota, 6), dtype=torch.float64, device=device), torch.empty((K, quota, M, P), dtype=torch.float64, device=device), dead[0], dead[1], dead[2],
+                torch.zeros(K, dtype=torch.int32, device=device), torch.ones(K, dtype=torch.int32, device=device))
+
+    def run(self, niterations, quota, buffers, stream=None):
+        """Enqueue ``niterations`` iterations of every run into the record ``buffers`` of a batch of ``quota`` records per run (asynchronous)."""
+        self._check(self._lib.dl_nested_run(self._handle, int(niterations), int(quota), *[ctypes.c_void_p(b.data_ptr()) for b in buffers], self._stream(stream)))
+
+    def close(self):
+        if getattr(self, '_handle', None):
+            self._lib.dl_nested_destroy(self._handle)
             self._handle = None
 
     def __del__(self):

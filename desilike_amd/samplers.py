@@ -1040,4 +1040,7 @@ def __getattr__(name):
     if name == 'SMCSampler':
         from . import smc
         return smc.SMCSampler
+    if name == 'NestedSampler':
+        from . import nested
+        return nested.NestedSampler
     raise AttributeError('module {!r} has no attribute {!r}'.format(__name__, name))

@@ -452,6 +452,47 @@ int  dl_smc_run(dl_smc* smc, int64_t niterations, int32_t quota, double* history
  * "n_steps" */
 int64_t dl_smc_info(const dl_smc* smc, const char* key);
 
+/* ---- device-resident batched nested sampling ----------------------------------------------------------------------------------------------------
+ * Nested sampling (Skilling 2006) on ``nruns`` independent runs of ``nlive`` live points resident on the GPU (csrc/dl_nested.h states the algorithm, the order of
+ * every sum and the random draws; none of the arithmetic of the dynesty, PolyChord or nautilus the reference wraps).  An iteration ranks the live points of a run,
+ * lets the ``ndelete`` lowest die with weights log w_j = log(X_{j-1} - X_j), log X_j = log X_{j-1} - 1 / (nlive - j), adds them to logZ, reseeds their slots from
+ * survivors and mutates those slots with ``n_steps`` random-walk Metropolis sweeps in the prior under the hard constraint L > L*, each ONE dl_eval_batch over all
+ * nruns x ndelete proposals.  A run goes to rest when the evidence left in its live points is below ``dlogz`` of the total.  Nothing in dl_nested_run allocates or
+ * synchronises, and the host never reads a mode to decide what to enqueue.  Errors: non-zero, message via dl_last_error(NULL). */
+typedef struct dl_nested dl_nested;
+/* nlive: a multiple of 64 in 64 .. 8192; the context has 1 .. 64 parameters; run_ids[nruns] global index of every run (NULL: 0 .. nruns - 1; keys the draws);
+ * offset: the constant of a posterior context (added to the reported logZ); widths[P] (host): the width or scale of every parameter's prior, positive (the
+ * proposal's fallback for a component without variance) */
+int  dl_nested_create(dl_nested** out, dl_ctx* ctx, int32_t nruns, int32_t nlive, const int32_t* run_ids, uint64_t seed, double offset, const double* widths);
+void dl_nested_destroy(dl_nested* nested);
+/* ndelete in 1 .. nlive / 2, n_steps sweeps per iteration (1 .. 1024), target_acceptance in (0, 1), dlogz in (0, 1), scale: the proposal scale of every run
+ * (replaces the adapted ones; 1e-3 .. 1e3); allocates where n_steps changes; synchronises */
+int  dl_nested_set_hyper(dl_nested* nested, int32_t ndelete, int32_t n_steps, double target_acceptance, double dlogz, double scale, void* hip_stream);
+/* host coords[nruns, nlive, P]: evaluates log-likelihood and log-prior; an error if a status is not 0 or a log-likelihood or log-prior is not finite (nested sampling
+ * has no meaning for a plateau at -inf: the caller redraws such rows).  log X = 0, logZ = -inf, counters = 0, every run climbing.  synchronises */
+int  dl_nested_set_live(dl_nested* nested, const double* coords, void* hip_stream);
+/* host arrays, all required: coords[nruns, nlive, P], loglike and logprior [nruns, nlive] (finite), logx, logz (without the offset; -inf before the first iteration),
+ * counters, scale [nruns], modes[nruns] (0 at rest, 1 climbing) -- what dl_nested_get_state returns: the run continues bit for bit.  synchronises */
+int  dl_nested_set_state(dl_nested* nested, const double* coords, const double* loglike, const double* logprior, const double* logx, const double* logz,
+                         const int64_t* counters, const double* scale, const int32_t* modes, void* hip_stream);
+/* host arrays (any may be NULL), as dl_nested_set_state; synchronises */
+int  dl_nested_get_state(dl_nested* nested, double* coords, double* loglike, double* logprior, double* logx, double* logz, int64_t* counters, double* scale,
+                         int32_t* modes, void* hip_stream);
+/* TEST AND DIAGNOSTIC ENTRY (no sampler needs it; tests/test_gpu_nested.py compares the device with the NumPy statement decision by decision through it): of the
+ * LAST iteration, host arrays (any may be NULL): ranks[nruns, nlive] (the slot of every rank), seeds[nruns, ndelete] (the slot that seeded the dead point of rank j),
+ * accepts[nruns, n_steps, ndelete] (0 / 1), mean[nruns, P], covariance[nruns, P, P] (lower triangle) of the survivors; synchronises */
+int  dl_nested_get_decisions(dl_nested* nested, int32_t* ranks, int32_t* seeds, uint8_t* accepts, double* mean, double* covariance, void* hip_stream);
+/* ``niterations`` iterations of every run, enqueued on ``hip_stream`` (asynchronous).  Every iteration of run k that is not at rest writes (log X, logZ + offset, L*,
+ * mean acceptance of its sweeps, scale, logZ_rem + offset) into row count_dev[k] of history_dev[nruns, quota, 6] and its ndelete dead points, in rank order, into slot
+ * count_dev[k] of coords_dev[nruns, quota, ndelete, P], loglike_dev, logprior_dev and logweight_dev [nruns, quota, ndelete]; mode_dev[nruns] holds the modes after the
+ * last iteration (0 at rest).  A run whose count_dev[k] reached ``quota`` waits.  The counts are NOT reset: the caller zeroes them at the start of a batch (how the
+ * calls are chunked does not change the runs). */
+int  dl_nested_run(dl_nested* nested, int64_t niterations, int32_t quota, double* history_dev, double* coords_dev, double* loglike_dev, double* logprior_dev,
+                   double* logweight_dev, int32_t* count_dev, int32_t* mode_dev, void* hip_stream);
+/* integer properties: "nruns", "nlive", "n_params", "ndelete", "iterations" (enqueued since the live points were set), "evaluations" (rows given to dl_eval_batch),
+ * "n_steps" */
+int64_t dl_nested_info(const dl_nested* nested, const char* key);
+
 /* ---- MLP emulator training ---------------------------------------------------------------------------------------
  * The reference trains its MLP emulators through the third-party engine ``cosmoprimo.emulators.tools.MLPEmulatorEngine`` (desilike/emulators/__init__.py:510-533;
  * network structure: emulators/conversion.py:20-96).  Here: fp64 mini-batch Adam on the mean squared error of the (already scaled) outputs, entirely on the device

@@ -29,6 +29,8 @@ struct DlOptions {
     bool no_emu_fused, no_gram_epilogue, step_kernel, chi2_fused, no_chi2_big;   // DL_NO_EMU_FUSED, DL_NO_GRAM_EPILOGUE, DL_STEP_KERNEL, DL_CHI2_FUSED, DL_NO_CHI2_BIG (dl_api.hip)
     bool fs_no_moments;   // DL_FS_NO_MOMENTS=1: the fast theory kernels on their interval-polynomial path (polynomial stage, output tile, knot loop without prefetch) where
                           // the moment form would apply (DlObsDev::moment_form; A/B measurements and the parity test of the two paths)
+    bool fs_mu_prio;      // DL_FS_MU_PRIO=0: the mu wave of the fast theory kernels without its raised priority (on by default: s_setprio 2 from entry to the barrier before the
+                          // evaluation phase; A/B measurements)
     int xcd_local;    // DL_XCD_LOCAL: 0 off, 1 chi2 GEMM path (default), 2 also the theory kernel's point order
     long long chi2_max_rows;   // DL_CHI2_GEMM_MAX (default 2048): above, the split-K / LDS-DMA GEMM paths
     int cg_mt;        // DL_CG_MT: forced row tile of the chi2 GEMM (0: chosen per batch)

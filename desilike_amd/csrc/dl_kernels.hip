@@ -65,6 +65,7 @@ static void dl_options_read() {
     auto flag = [](const char* name) { const char* v = std::getenv(name); return v != nullptr && atoi(v) != 0; };
     o.no_emu_fused = on("DL_NO_EMU_FUSED"); o.no_gram_epilogue = on("DL_NO_GRAM_EPILOGUE"); o.no_chi2_big = on("DL_NO_CHI2_BIG");
     o.fs_no_moments = flag("DL_FS_NO_MOMENTS");
+    o.fs_mu_prio = std::getenv("DL_FS_MU_PRIO") ? atoi(std::getenv("DL_FS_MU_PRIO")) != 0 : true;
     o.step_kernel = flag("DL_STEP_KERNEL"); o.chi2_fused = flag("DL_CHI2_FUSED"); o.chi2_bfrag = flag("DL_CHI2_BFRAG");
     o.xcd_local = std::getenv("DL_XCD_LOCAL") ? atoi(std::getenv("DL_XCD_LOCAL")) : 1;
     o.chi2_max_rows = std::getenv("DL_CHI2_GEMM_MAX") ? atoll(std::getenv("DL_CHI2_GEMM_MAX")) : 2048;
@@ -77,6 +78,14 @@ extern "C" void dl_options_refresh(void) { (void)dl_options(); dl_options_read()
 
 // Workgroups are dealt round-robin to the 8 XCDs; with xblk > 0 workgroup w = xcd + 8 r handles point xblk (xcd + 8 (r / xblk)) + r % xblk (see dl_fullshape_body)
 __device__ __forceinline__ int dl_fs_point_of_wg(int wg, int xblk) { return xblk ? xblk * ((wg & 7) + 8 * ((wg >> 3) / xblk)) + ((wg >> 3) % xblk) : wg; }
+
+// Flags of the theory launches, in the kernels' `stop_after` / `flags` argument: bits 0-7 diagnostic stop (DL_FS_STOP; then nothing else is set), 8-15 xblk,
+// 16 raised priority of the mu wave
+#define DL_FS_FLAG_PRIO (1 << 16)
+#define DL_FS_STAMP_SLOTS 10
+#define DL_HWREG_HW_ID ((31 << 11) | 4)     // s_getreg operand: 32 bits from bit 0 of HW_REG_HW_ID: wave [3:0], SIMD [5:4], pipe [7:6], CU [11:8], shader array [12], shader engine [15:13]
+#define DL_HWREG_XCC_ID ((31 << 11) | 20)   // HW_REG_XCC_ID: XCC [3:0]
+static int dl_fs_launch_flags(int xblk, int stop_after) { return stop_after != 0 ? stop_after : (xblk << 8) | (dl_options().fs_mu_prio ? DL_FS_FLAG_PRIO : 0); }
 
 // SUB: the point is evaluated by a 256-thread SUB-GROUP of a larger workgroup (dl_step_kernel: four points per 1024-thread workgroup): `lds_sub`, `tid_sub`, `b_sub` name its
 // share of LDS, the thread's index in the sub-group and the point; every sub-group runs the same sequence of barriers (the branches between them are uniform in the observable).
@@ -93,20 +102,25 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
     double* lds = SUB ? lds_sub : lds_wg;
     // Workgroups are dealt round-robin to the 8 XCDs; the GEMM that follows runs row block mb (xblk = 32 or 64 points) on XCD mb % 8.  With xblk > 0 the points are dealt
     // so that a row block is PRODUCED on the XCD that consumes it (B a multiple of 8 xblk): workgroup w = xcd + 8 r handles point xblk (xcd + 8 (r / xblk)) + r % xblk.
-    const int xblk = SUB ? 0 : (stop_after >> 8) & 0xff;
-    stop_after = (SUB || xblk) ? 0 : stop_after;
+    // `stop_after` carries the launcher's flags (dl_fs_launch_flags): a diagnostic stop (DL_FS_STOP, then nothing else), or xblk | priority
+    const int flags = (SUB || (stop_after & ~0xff) == 0 || stop_after < 0) ? 0 : stop_after;
+    const int xblk = (flags >> 8) & 0xff;
+    stop_after = (SUB || flags) ? 0 : stop_after;
     const int b = SUB ? b_sub : dl_fs_point_of_wg(blockIdx.x, xblk);
-    // DL_FS_STAMPS diagnostics: s_memtime (shader clock) of thread 0 at entry, after each barrier and at exit, 8 slots per workgroup
-#define DL_STAMP(slot) if (stamps != nullptr && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memtime();
+    const int tid = SUB ? tid_sub : (int)threadIdx.x, nthr = NT;
+    // DL_FS_STAMPS diagnostics: s_memtime (shader clock) of thread 0 at entry, after each barrier and at exit, 8 slots per workgroup; slots 8, 9: the hardware ids
+    // (XCC id << 32 | HW_ID: SIMD, CU, shader engine) of the waves of thread 0 and of the mu wave
+#define DL_STAMP(slot) if (stamps != nullptr && tid == 0) stamps[(size_t)blockIdx.x * DL_FS_STAMP_SLOTS + (slot)] = __builtin_amdgcn_s_memtime();
+#define DL_STAMP_HWID(slot) stamps[(size_t)blockIdx.x * DL_FS_STAMP_SLOTS + (slot)] = ((unsigned long long)__builtin_amdgcn_s_getreg(DL_HWREG_XCC_ID) << 32) | __builtin_amdgcn_s_getreg(DL_HWREG_HW_ID);
     DL_STAMP(0)
-    if (stamps != nullptr && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memrealtime();   // 100 MHz, same on every XCD
+    if (stamps != nullptr && tid == 0) { stamps[(size_t)blockIdx.x * DL_FS_STAMP_SLOTS + 6] = __builtin_amdgcn_s_memrealtime(); DL_STAMP_HWID(8) }   // 100 MHz, same on every XCD
+    if (FAST && stamps != nullptr && tid == NT - 64) { DL_STAMP_HWID(9) }
     // FAST instantiations are only launched when the convolution path applies (or the spline is fixed): the segmented sweeps are not compiled in
     const bool toep = !o.fixed_spline && (FAST || o.toeplitz);
     static_assert(!MOM || (FAST && !EFT && !DENSE), "the moment form belongs to the pair evaluation");
     const DlFsShared s = MOM ? dl_fs_shared_carve_mom(lds, o) : dl_fs_shared_carve(lds, o.n_t, o.n_in, dl_fs_n_dd0(o), toep);
     const bool direct = MOM && dl_fs_mom_direct(o);
     const double* th = TH_ROW ? th_row : theta + (size_t)b * n_params;
-    const int tid = SUB ? tid_sub : (int)threadIdx.x, nthr = NT;
     if (stop_after == -1) return;  // stop_after != 0: timing diagnostics only (DL_FS_STOP), outputs are then incomplete
     // constants of the later phases are requested now: their round trip hides behind phase 0/1
     double lk_pref[DL_P3_PREF];
@@ -117,6 +131,13 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
         // per phase (its results are first read in phase 3), lane 63 of it keeps the per-point scalars.
         constexpr int KT = NT - 64;       // (DL_FS_KT at 256 threads)
         const bool mu_wave = tid >= KT;
+        // The mu wave's dependent chain (square root, two logarithms, a division) sets the length of the phases, and with four workgroups on a CU the wave shares its
+        // SIMD with three spline waves of the other workgroups (the dispatcher starts each workgroup of a CU on another SIMD: DL_FS_STAMPS placement table): it goes
+        // first there until the evaluation phase.  The 256-thread pair-evaluation forms only (plain, several observables, folded ensemble: where it was measured);
+        // DL_FS_MU_PRIO=0: no raised priority.  A scheduling hint: no result depends on it.
+        constexpr bool PRIO = !SUB && !EFT && !DENSE && NT == DL_FS_THREADS;
+        const bool mu_prio = PRIO && (flags & DL_FS_FLAG_PRIO) && __builtin_amdgcn_readfirstlane(tid) >= KT;
+        if (mu_prio) __builtin_amdgcn_s_setprio(2);
         const int m = tid - KT;                                  // mu node of this lane of the mu wave
         const bool mu_lane = mu_wave && m < o.n_mu, scalar_lane = (tid == nthr - 1);
         DlMuCarry c;
@@ -158,6 +179,7 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
             DL_STAMP(3)
             if (stop_after == 5) return;
         }
+        if (mu_prio) __builtin_amdgcn_s_setprio(0);
     } else {
         dl_fs_phase01(tid, nthr, o, th, s);
         __syncthreads();
@@ -203,8 +225,9 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
         DL_STAMP(4)   // (thread 0's own evaluation and stores: no barrier on this path, the stamp is not the workgroup's)
     }
     DL_STAMP(5)
-    if (stamps != nullptr && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memrealtime();
+    if (stamps != nullptr && tid == 0) stamps[(size_t)blockIdx.x * DL_FS_STAMP_SLOTS + 7] = __builtin_amdgcn_s_memrealtime();
 #undef DL_STAMP
+#undef DL_STAMP_HWID
 }
 
 template <bool FAST, int NL, bool EFT, bool DENSE = false, bool MOM = false>
@@ -408,7 +431,7 @@ bool dl_launch_fullshape_ens(const DlObsDev* obs_host, int n_obs, const DlObsDev
     for (int i = 0; i < n_obs; ++i) shmem = std::max(shmem, dl_fs_fast_shared_bytes(obs_host[i], mom));
     auto launch = [&](auto kernel) {
         if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        const int flags = (xcd_block > 0 && B % (8 * xcd_block) == 0) ? (xcd_block << 8) : 0;
+        const int flags = dl_fs_launch_flags((xcd_block > 0 && B % (8 * xcd_block) == 0) ? xcd_block : 0, 0);
         const int n_extra = f.pend.half >= 0 ? (int)((B + DL_ENS_SLOTS_PER_WG - 1) / DL_ENS_SLOTS_PER_WG) : 0;   // workgroups that write the state after the pending accepts
         DL_LAUNCH(kernel, dim3((unsigned)(B + n_extra), (unsigned)n_obs), dim3(DL_FS_THREADS), shmem, stream, obs_dev, f, power, ld_power, flags, (int)B);
     };
@@ -637,7 +660,7 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
     static const char* stamp_file = getenv("DL_FS_STAMPS");
     static unsigned long long* stamps_dev = nullptr;
     static int stamp_launches = 0;
-    if (stamp_file && !stamps_dev) { (void)hipMalloc((void**)&stamps_dev, (size_t)65536 * 8 * sizeof(unsigned long long)); }
+    if (stamp_file && !stamps_dev) { (void)hipMalloc((void**)&stamps_dev, (size_t)65536 * DL_FS_STAMP_SLOTS * sizeof(unsigned long long)); }
     unsigned long long* stamps = (stamp_file && B >= 256 && B <= 65536 && stamp_launches >= 30 && stamp_launches < 34) ? stamps_dev : nullptr;
     if (stamp_file && B >= 256) stamp_launches++;
     // all observables in one launch when they share a fast instantiation (same multipole count class, no counter terms, no separate tables, same LDS footprint class)
@@ -656,7 +679,7 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
             for (int i = 0; i < n_obs; ++i) shmem = std::max(shmem, dl_fs_fast_shared_bytes(obs_host[i], mom));
             auto launch = [&](auto kernel) {
                 if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                const int flags = (xcd_block > 0 && B % (8 * xcd_block) == 0) ? (xcd_block << 8) : 0;
+                const int flags = dl_fs_launch_flags((xcd_block > 0 && B % (8 * xcd_block) == 0) ? xcd_block : 0, 0);
                 DL_LAUNCH(kernel, dim3((unsigned)B, (unsigned)n_obs), dim3(DL_FS_THREADS), shmem, stream, obs_dev, theta, n_params, power, ld_power, flags);
             };
             if (nl3) { if (dense) launch(dl_fullshape_multi_kernel<true, 3, false, true>); else if (mom) launch(dl_fullshape_multi_kernel<true, 3, false, false, true>); else launch(dl_fullshape_multi_kernel<true, 3, false>); }
@@ -709,14 +732,14 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
         size_t shmem = generic ? dl_fs_shared_doubles_obs(oh, false) * sizeof(double) : dl_fs_fast_shared_bytes(oh, mom);
         auto launch = [&](auto kernel) {
             if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);  // e.g. 2000-knot BAO tables
-            const int flags = (xcd_block > 0 && stop_after == 0 && B % (8 * xcd_block) == 0) ? (xcd_block << 8) : stop_after;
+            const int flags = dl_fs_launch_flags((xcd_block > 0 && B % (8 * xcd_block) == 0) ? xcd_block : 0, stop_after);
             DL_LAUNCH(kernel, dim3((unsigned)B), dim3(DL_FS_THREADS), shmem, stream, obs_host[i], theta, n_params, power, ld_power, tables, ld_tables, flags, stamps);
             if (stamps) {
                 (void)hipStreamSynchronize(stream);
-                std::vector<unsigned long long> h((size_t)B * 8);
+                std::vector<unsigned long long> h((size_t)B * DL_FS_STAMP_SLOTS);
                 (void)hipMemcpy(h.data(), stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
                 if (FILE* f = fopen(stamp_file, "a")) {
-                    for (int64_t w = 0; w < B; ++w) { for (int q = 0; q < 8; ++q) fprintf(f, "%llu ", h[(size_t)w * 8 + q]); fprintf(f, "\n"); }
+                    for (int64_t w = 0; w < B; ++w) { for (int q = 0; q < DL_FS_STAMP_SLOTS; ++q) fprintf(f, "%llu ", h[(size_t)w * DL_FS_STAMP_SLOTS + q]); fprintf(f, "\n"); }
                     fprintf(f, "#\n");
                     fclose(f);
                 }
@@ -725,7 +748,7 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
         if (wide) {
             auto launch_wide = [&](auto kernel) {
                 if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                const int flags = (xcd_block > 0 && stop_after == 0 && B % (8 * xcd_block) == 0) ? (xcd_block << 8) : stop_after;
+                const int flags = dl_fs_launch_flags((xcd_block > 0 && B % (8 * xcd_block) == 0) ? xcd_block : 0, stop_after);
                 DL_LAUNCH(kernel, dim3((unsigned)B), dim3(512), shmem, stream, obs_host[i], theta, n_params, power, ld_power, flags, stamps);
             };
             if (nl3) { if (mom) launch_wide(dl_fullshape_wide_kernel<3, true>); else launch_wide(dl_fullshape_wide_kernel<3>); }

@@ -239,6 +239,8 @@ int  dl_profile_read(dl_ctx* ctx, double* ms, int32_t n);
  *     DL_MH_NO_DEFER, DL_HOST_MODE (0 - 4: how the *_host entry points wait, see dl_eval_batch_host)
  *     DL_FS_NO_MOMENTS (the fast full-shape kernels on their interval-polynomial path where the moment form would apply: agrees with the default to rounding, ~1e-15 of a row's
  *     largest value, not bit for bit -- tests/test_gpu_fullshape_moments.py compares the two)
+ *     DL_FS_MU_PRIO=0 (the fast full-shape kernels without the raised priority of the wave that runs the per-mu chain: a scheduling hint, bit-identical results --
+ *     tests/test_gpu_fullshape_balance.py)
  *   diagnostics (in-kernel time stamps written to the named file, per-phase early exits; they synchronise: never set in production):
  *     DL_FS_STAMPS, DL_FS_STOP, DL_CG_STAMPS, DL_EF_STAMPS, DL_FM_STAMPS, DL_STK_STAMPS, DL_STEP_STAMPS, DL_ENS_STAMPS, DL_ENS_FOLD_STAMPS
  *   environment of the collectives: DL_RCCL_PATH, DL_COMM_TIMEOUT (desilike_amd/parallel.py, bench.py) */

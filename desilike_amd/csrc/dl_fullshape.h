@@ -66,6 +66,7 @@
 #define DL_FIR_TAPS { -0.7320508075688774, 0.4641016151377547, -0.12435565298214114, 0.033320996790809666, -0.008928334181097484, 0.002392339933580261, -0.0006410255532235571, 0.0001717622793139658, -4.602356403230609e-05, 1.2331976815258487e-05, -3.3043432287278414e-06, 8.85396099652874e-07, -2.3724116988365352e-07, 6.356857988173978e-08, -1.7033149643305495e-08, 4.564018691482174e-09, -1.2229251226231984e-09, 3.2768179901061786e-10, -8.780207341927256e-11, 2.3526494666472232e-11, -6.303905246616353e-12, 1.6891263199931699e-12, -4.5260003335632413e-13, 1.212738134321263e-13, -3.24952203721809e-14, 8.707068056597241e-15, -2.333051854208057e-15, 6.251393602349824e-16, -1.675055867318723e-16 }
 #define DL_FIR_MU (-0.2679491924311228)       // sqrt(3) - 2
 #define DL_FIR_LN_ABS_MU (-1.3169578969248164)
+#define DL_PS_HEAD 8       // doubles of the header of the phase-shift tables (dl_ps_tab)
 #define DL_SEG_QMAX 12     // dot-product terms per thread: warm-up length <= DL_SEG_PARTS * DL_SEG_QMAX = 48
 
 struct DlInput {
@@ -102,8 +103,8 @@ struct DlObsDev {
     // band template (template kind 3, power_template.py:893-961): P_tt = P_tt_fid (1 + sum_i (dptt_i - 1) tent_i(k)), P_dd = P_tt / f^2
     int32_t n_band, moment_form;           // moment_form (fast uniform-knot kernels without counter terms): bit 0: the spline is evaluated from (knot value, moment)
                                            // records on the exactly uniform grid (knot table uniform to rounding: see dl_host.hpp); bit 1: knot_rec is filled
-    DlInput band_in[DL_MAX_BAND];
-    const double* band_tab;                // [n_band][n_t] tent functions at the knots
+    DlInput band_in[DL_MAX_BAND];          // (template kind 4, BAO phase shift: band_in[0] is the baoshift input -- dl_ps_baoshift)
+    const double* band_tab;                // [n_band][n_t] tent functions at the knots (template kind 4: the phase-shift tables -- dl_ps_tab)
     // tracer-velocity variant of the PNG theory (primordial_non_gaussianity.py:196-330): P = jac fog (b + f mu'^2) (bv f mu' velfac / k') P(k'), fog = sinc(sigmau k') / (1 + sigmas^2 k'^2 mu'^2 / 2)
     int32_t png_vel, pad_vel;
     DlInput bv, sigmau;
@@ -372,7 +373,7 @@ DL_HD void dl_fs_knots(int tid, int nthr, const DlObsDev& o, const double* th, c
         const double df = dl_get(o.df, th), inv_df2 = 1. / (df * df);
         for (int j = tid; j < n_t; j += nthr) {
             double factor = 1.;
-            for (int i = 0; i < o.n_band; ++i) factor += (dl_get(o.band_in[i], th) - 1.) * o.band_tab[(size_t)i * n_t + j];
+            for (int i = 0; i < o.n_band; ++i) factor += (dl_get(o.band_in[i], th) - 1.) * o.band_tab[(size_t)i * n_t + j];   // (n_band is 0 for template kind 4, which borrows band_in[0] / band_tab: dl_ps_baoshift)
             s.y[j] = o.pk_fid[j] * factor * inv_df2;
         }
     } else {
@@ -1050,6 +1051,116 @@ DL_HD void dl_bao_phaseA(int tid, int nthr, const DlObsDev& o, const double* th,
     }
 }
 
+// ---- BAO phase-shift template (template kind 4): per-point wiggle spline ---------------------------------------------------------------
+// BAOPhaseShiftPowerSpectrumTemplate.calculate (power_template.py:487-492): the wiggle at the template knots is a cubic interpolation of a CONSTANT table (the
+// fiducial P_dd - P_now on an inner geomspace grid) at the shifted wavenumbers clip(k_t + (baoshift - 1) kshift_t); the theory then splines those knot values again
+// (bao.py:121-125).  Per point: knot values (dl_bao_ps_knots), their not-a-knot moments on the uniform knots by the convolution of dl_fs_phase2_fir
+// (dl_bao_ps_fir), end corrections and end relations (dl_bao_ps_end_*); phase B evaluates the wiggle from (knot value, moment) pairs (dl_bao_ps_wiggle, the cubic
+// of dl_spline_eval_m).  LDS behind the BAO kernel's own: mu^k table [2 DL_FIR_PAD + 2] | moments m_j = M_j h^2 / 6 [n_t] | zero-padded knot values
+// [DL_FIR_PAD + n_t + DL_FIR_PAD] -- 8 (2 n_t + 130) bytes: 33.0 KB at the reference's 2000 knots.
+// Template kinds 3 and 4 exclude each other, and DlObsDev travels by value with every launch of every theory kernel: the phase-shift template borrows the band template's
+// input slot and table pointer instead of growing the struct.  The table: header [DL_PS_HEAD] (clip bounds kmin, kmax; log10 k of the first inner knot; 1 / spacing of
+// the inner grid in log10 k; last interval index n_w - 2) | knot records [n_t][2]: (k_t, kshift) | [n_w - 1][4] interval polynomials of the inner wiggle table in the
+// fractional index -- all in the arena.
+DL_HD const DlInput& dl_ps_baoshift(const DlObsDev& o) { return o.band_in[0]; }
+DL_HD const double* dl_ps_tab(const DlObsDev& o) { return o.band_tab; }
+
+struct DlPsShared {
+    double* mupow;  // [2 DL_FIR_PAD + 1] mu^k, mu = sqrt(3) - 2
+    double* m;      // [n_t]
+    double* y;      // [n_t], DL_FIR_PAD zeros either side
+};
+DL_HD size_t dl_bao_ps_offset(int n_in) { return (DL_BAO_PT + (size_t)n_in + 1) & ~(size_t)1; }
+DL_HD size_t dl_bao_ps_shared_doubles(int n_t, int n_in) { return dl_bao_ps_offset(n_in) + (2 * DL_FIR_PAD + 2) + 2 * (size_t)n_t + 2 * DL_FIR_PAD; }
+DL_HD DlPsShared dl_bao_ps_carve(double* lds, int n_t, int n_in) {
+    DlPsShared s;
+    s.mupow = lds + dl_bao_ps_offset(n_in);
+    s.m = s.mupow + 2 * DL_FIR_PAD + 2;
+    s.y = s.m + n_t + DL_FIR_PAD;
+    return s;
+}
+
+// wiggle at the knots: every thread takes knots tid, tid + nthr, ... (any workgroup size); zero padding and the mu^k table beside it
+DL_HD void dl_bao_ps_knots(int tid, int nthr, const DlObsDev& o, const double* th, const DlPsShared& s) {
+    const int n = o.n_t;
+    const double* head = dl_ps_tab(o);
+    const double* rec = head + DL_PS_HEAD;
+    const double* coef = rec + 2 * (size_t)n;
+    const double kmin = head[0], kmax = head[1], x0 = head[2], inv_h = head[3];
+    const int jmax = (int)head[4];
+    const double shift = dl_get(dl_ps_baoshift(o), th) - 1.;
+    for (int i = tid; i < n; i += nthr) {
+        double x = fma(shift, rec[2 * i + 1], rec[2 * i]);
+        // the clip comes BEFORE the logarithm: the shifted wavenumber is negative at the low end of the baoshift prior.  Comparisons, not fmin / fmax: a NaN baoshift stays
+        // NaN as under np.clip (the knot value, the spline and the multipoles are then NaN; the finalize kernels flag the NaN parameter itself: every theta column is checked)
+        x = x < kmin ? kmin : (x > kmax ? kmax : x);
+        const double t = (log10(x) - x0) * inv_h;
+        int j = (int)(t > 0. ? t : 0.);              // (0 for a NaN abscissa: u and the value below are NaN)
+        j = j > jmax ? jmax : j;
+        const double u = t - (double)j;
+        const double* c = coef + 4 * (size_t)j;
+        s.y[i] = fma(fma(fma(c[3], u, c[2]), u, c[1]), u, c[0]);
+    }
+    for (int i = tid; i < 2 * DL_FIR_PAD; i += nthr) s.y[i < DL_FIR_PAD ? i - DL_FIR_PAD : n + i - DL_FIR_PAD] = 0.;
+    for (int k = tid; k <= 2 * DL_FIR_PAD; k += nthr) {
+        const double v = exp((double)k * DL_FIR_LN_ABS_MU);
+        s.mupow[k] = (k & 1) ? -v : v;
+    }
+}
+
+// m_j = sum_e t_|e| y_{j+e}: the solution of m_{j-1} + 4 m_j + m_{j+1} = y_{j-1} - 2 y_j + y_{j+1} on the infinite grid (see dl_fs_phase2_fir); four consecutive knots
+// per thread from one sliding window
+DL_HD void dl_bao_ps_fir(int tid, int nthr, const DlObsDev& o, const DlPsShared& s) {
+    const double T[DL_FIR_D + 1] = DL_FIR_TAPS;
+    const int n = o.n_t;
+    for (int j0 = 4 * tid; j0 < n; j0 += 4 * nthr) {
+        double acc[4] = {0., 0., 0., 0.};
+        const double* yp = s.y + j0 - DL_FIR_D;   // knot j0 - D + p: down to y[-DL_FIR_D], up to y[n + 2 + DL_FIR_D] (inside the padding)
+#pragma unroll
+        for (int p = 0; p < 2 * DL_FIR_D + 4; ++p) {
+            const double v = yp[p];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int e = p - DL_FIR_D - q;
+                if (e >= -DL_FIR_D && e <= DL_FIR_D) acc[q] = fma(T[e < 0 ? -e : e], v, acc[q]);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (j0 + q < n) s.m[j0 + q] = acc[q];
+    }
+}
+
+// End corrections: m_j += a mu^(j-1) + b mu^(n-2-j) with a, b from the not-a-knot rows m_1 = r_1 / 6, m_{n-2} = r_{n-2} / 6 (dl_fs_phase2d_toep, in units of h^2 / 6).
+// Threads 0 .. 2 DL_FIR_PAD - 1 (every workgroup has at least 64) take one knot each: 1 .. DL_FIR_PAD from the left, n-2 .. n-1-DL_FIR_PAD from the right (n >= 4
+// DL_FIR_PAD: disjoint; beyond them the correction is below rounding).  a and b read m_1 and m_{n-2}, which are themselves corrected: every thread computes its value
+// (dl_bao_ps_end_moment), a barrier, then the stores (dl_bao_ps_end_store), a barrier, then the end relations for m_0, m_{n-1} (dl_bao_ps_end_relations).
+DL_HD int dl_bao_ps_end_knot(int tid, int n) { return tid < DL_FIR_PAD ? 1 + tid : n - 2 - (tid - DL_FIR_PAD); }
+DL_HD double dl_bao_ps_end_moment(int tid, const DlObsDev& o, const DlPsShared& s) {
+    if (tid >= 2 * DL_FIR_PAD) return 0.;
+    const int n = o.n_t, i = dl_bao_ps_end_knot(tid, n);
+    const double a = ((s.y[0] - s.y[1]) - (s.y[1] - s.y[2])) * (1. / 6.) - s.m[1];
+    const double b = ((s.y[n - 3] - s.y[n - 2]) - (s.y[n - 2] - s.y[n - 1])) * (1. / 6.) - s.m[n - 2];
+    const int kl = i - 1, kr = n - 2 - i;
+    return s.m[i] + a * (kl <= 2 * DL_FIR_PAD ? s.mupow[kl] : 0.) + b * (kr <= 2 * DL_FIR_PAD ? s.mupow[kr] : 0.);
+}
+DL_HD void dl_bao_ps_end_store(int tid, const DlObsDev& o, const DlPsShared& s, double value) {
+    if (tid < 2 * DL_FIR_PAD) s.m[dl_bao_ps_end_knot(tid, o.n_t)] = value;
+}
+DL_HD void dl_bao_ps_end_relations(int tid, const DlObsDev& o, const DlPsShared& s) {
+    const int n = o.n_t;
+    if (tid == 0) s.m[0] = o.end0a * s.m[1] + o.end0b * s.m[2];
+    if (tid == 1) s.m[n - 1] = o.end1a * s.m[n - 2] + o.end1b * s.m[n - 3];
+}
+
+// wiggle on interval j at the fractional index u (0 <= j <= n_t - 2; u outside [0, 1] continues the end pieces):
+//   S = y_j + u [(y_j+1 - y_j) - (2 m_j + m_j+1) + u (3 m_j + u (m_j+1 - m_j))]
+DL_HD double dl_bao_ps_wiggle(const DlPsShared& s, int j, double u) {
+    const double y0 = s.y[j], y1 = s.y[j + 1], m0 = s.m[j], m1 = s.m[j + 1];
+    const double c1 = (y1 - y0) - fma(2., m0, m1);
+    return fma(u, fma(u, fma(u, m1 - m0, 3. * m0), c1), y0);
+}
+
 // 1 / x for x >= 1, to rounding: hardware seed + two Newton steps on the device (6 instructions against ~20 of the IEEE division).  x is clamped to 1e300 first:
 // the Newton step of an infinite x would be inf * 0 (the callers square the result: 1e-600 is the same 0 as 1 / inf^2; a NaN x only comes from NaN inputs, which
 // the finalize kernels flag on their own)
@@ -1068,8 +1179,10 @@ DL_HD double dl_rcp(double x) {
 // 'standard' model on uniform knots (the reference's BAO templates: geomspace tables), bao.py:117-136 -- same formula as dl_bao_phaseB_m<0>, with everything that
 // depends on mu only taken from the per-mu records of phase A (LDS broadcasts: no global loads of nodes / weights in the loop), the abscissa in units of the knot
 // spacing (one add, integer clamp), the Finger-of-God factor 1 / (1 + (sigmas k mu)^2 / 2)^2 through dl_rcp.  NL = multipole accumulators compiled in.
-template <int NL>
+// PS: the wiggle comes from the point's own spline in LDS (phase-shift template, dl_bao_ps_*) instead of the constant o.coef_w.
+template <int NL, bool PS = false>
 DL_HD void dl_bao_phaseB_std(int tid, int nthr, const DlObsDev& o, double* lds) {
+    const DlPsShared ps = PS ? dl_bao_ps_carve(lds, o.n_t, o.n_in) : DlPsShared();
     const double qper = lds[DL_BAO_QPER], b1 = lds[DL_BAO_B1];
     const int n_kin = o.n_kin, nm2 = o.n_t - 2;
     const int reciso = (o.bao_mode & 15) == 1;
@@ -1090,7 +1203,7 @@ DL_HD void dl_bao_phaseB_std(int tid, int nthr, const DlObsDev& o, double* lds) 
             j = j < 0 ? 0 : (j > nm2 ? nm2 : j);
             const double u = t - (double)j;
             const double* c = o.coef_w + 4 * (size_t)j;
-            const double pkw = fma(fma(fma(c[3], u, c[2]), u, c[1]), u, c[0]);                     // [P_dd - P_now](k')
+            const double pkw = PS ? dl_bao_ps_wiggle(ps, j, u) : fma(fma(fma(c[3], u, c[2]), u, c[1]), u, c[0]);   // [P_dd - P_now](k')
             const double ca = fma(rec[4], omsk, b1), cb = fma(rec[3], omsk, b1);                   // b1 + f mu'^2 (1 - S(k)), b1 + f mu^2 (1 - S(k))
             const double Cap = ca * ca * exp(-(kq2 * rec[1]));                                     // bao.py:129-132
             const double r = dl_rcp(fma(kk2, rec[2], 1.));                                         // bao.py:133
@@ -1124,12 +1237,13 @@ DL_HD void dl_bao_phaseB_std(int tid, int nthr, const DlObsDev& o, double* lds) 
     }
 }
 
-template <int MODEL>   // 0: 'standard', 1: 'fix-damping' / 'move-all' / 'fog-damping' family, 2: resummed wiggles, 3: flexible wiggles
+template <int MODEL, bool PS = false>   // 0: 'standard', 1: 'fix-damping' / 'move-all' / 'fog-damping' family, 2: resummed wiggles, 3: flexible wiggles; PS: see dl_bao_phaseB_std
 DL_HD void dl_bao_phaseB_m(int tid, int nthr, const DlObsDev& o, double* lds) {
     if (MODEL == 0 && o.uniform_knots && o.n_mu <= DL_MAX_MU - 3) {
-        if (o.n_ell <= 3) dl_bao_phaseB_std<3>(tid, nthr, o, lds); else dl_bao_phaseB_std<DL_MAX_ELL>(tid, nthr, o, lds);
+        if (o.n_ell <= 3) dl_bao_phaseB_std<3, PS>(tid, nthr, o, lds); else dl_bao_phaseB_std<DL_MAX_ELL, PS>(tid, nthr, o, lds);
         return;
     }
+    const DlPsShared ps = PS ? dl_bao_ps_carve(lds, o.n_t, o.n_in) : DlPsShared();
     const double qper = lds[DL_BAO_QPER], f = lds[DL_BAO_F], b1 = lds[DL_BAO_B1], sigmas = lds[DL_BAO_SIGS];
     const int n_ell = o.n_ell, n_mu = o.n_mu, n_kin = o.n_kin, n_mu4 = (o.n_mu + 3) & ~3;
     const int reciso = (o.bao_mode & 15) == 1, model = o.bao_mode >> 4;
@@ -1163,7 +1277,7 @@ DL_HD void dl_bao_phaseB_m(int tid, int nthr, const DlObsDev& o, double* lds) {
                 double u;
                 dl_spline_locate<false>(o, lk + lds[DL_BAO_LQ + m], j, u);
                 const double* c = o.coef_w + 4 * (size_t)j;
-                double pkw = fma(fma(fma(c[3], u, c[2]), u, c[1]), u, c[0]);                    // [P_dd - P_now](k')
+                double pkw = PS ? dl_bao_ps_wiggle(ps, j, u) : fma(fma(fma(c[3], u, c[2]), u, c[1]), u, c[0]);   // [P_dd - P_now](k')
                 double kap = kq * lds[DL_BAO_FAC + m];
                 double mup2 = lds[DL_BAO_MUP2 + m];
                 double mu = (m < n_mu) ? o.mu[m] : 0.;

@@ -473,7 +473,11 @@ inline bool dl_build_obs(const dl_config& cfg, int iobs, int n_params, DlObsHost
             d.band_in[i].col = (int)std::lround(bin[2 * i]); d.band_in[i].value = bin[2 * i + 1];
             if (d.band_in[i].col >= n_params) { err = p + "in.band: theta column out of range"; return false; }
         }
-    } else if (d.templ < 0 || d.templ > 3) { err = p + "unknown template kind"; return false; }
+    } else if (d.templ == 4) {
+        if (d.theory != 2) { err = p + "phase-shift template: BAO wiggle theories only (its parameter moves the wiggles, which only they evaluate apart)"; return false; }
+        d.band_in[0] = dl_input_from(cfg, p + "in.baoshift", 1.);   // (dl_ps_baoshift: the band template's first slot)
+        if (d.band_in[0].col >= n_params) { err = p + "in.baoshift: theta column out of range"; return false; }
+    } else if (d.templ < 0 || d.templ > 4) { err = p + "unknown template kind"; return false; }
     // template knots in log10 k (full_shape.py:498: interp1d(log10(kap), log10(k11), pk11))
     std::vector<double> x_t(d.n_t), sf_th(d.n_t), sf_lg(d.n_t), lkin(d.n_kin);
     for (int j = 0; j < d.n_t; ++j) {
@@ -591,6 +595,55 @@ inline bool dl_build_obs(const dl_config& cfg, int iobs, int n_params, DlObsHost
             pknow_k[i] = std::fma(std::fma(std::fma(c[3], u, c[2]), u, c[1]), u, c[0]);
         }
     }
+    // phase-shift template (power_template.py:487-492): knot records (k_t, kshift) and the interval polynomials of the inner wiggle table -- not-a-knot in log10 k, the
+    // solver of the fixed tables, re-expanded in the fractional index of the exactly uniform inner grid (dl_fs_phase2d)
+    std::vector<double> ps_tab(2, 0.);
+    if (d.templ == 4) {
+        const auto& kshift = cfg.F(p + "ps_kshift");
+        const auto& kw = cfg.F(p + "ps_k");
+        const auto& wtab = cfg.F(p + "ps_wiggles");
+        const auto& klim = cfg.F(p + "ps_klim");
+        const int nw = (int)kw.size();
+        if (!d.toeplitz) {
+            err = p + (getenv("DL_NO_TOEPLITZ") ? "phase-shift template: its per-point spline needs the convolution path, which the diagnostics switch DL_NO_TOEPLITZ turns off: unset it"
+                                                : "phase-shift template: the template knots k_t must be uniform in log10 k to rounding (a geomspace table of at least 128 knots)");
+            return false;
+        }
+        if ((int)kshift.size() != d.n_t) { err = p + "phase-shift template: ps_kshift must have one entry per template knot"; return false; }
+        if (nw < 5 || (int)wtab.size() != nw) { err = p + "phase-shift template: ps_k and ps_wiggles (inner wiggle table, at least 5 knots) sizes differ"; return false; }
+        if (!klim.empty() && klim.size() != 2) { err = p + "phase-shift template: ps_klim holds the two clip bounds"; return false; }
+        std::vector<double> xw(nw);
+        for (int j = 0; j < nw; ++j) {
+            if (!(kw[j] > 0.)) { err = p + "phase-shift template: ps_k must be positive"; return false; }
+            xw[j] = std::log10(kw[j]);
+        }
+        DlSplineSetup spw;
+        if (!dl_spline_setup(xw, spw, err)) { err = p + "phase-shift template: ps_k: " + err; return false; }
+        DlObsDev tmp = d;
+        tmp.n_t = nw; tmp.uniform_knots = 1;
+        tmp.x0 = xw[0]; tmp.inv_hx = (nw - 1) / (xw[nw - 1] - xw[0]);
+        tmp.end0a = spw.end0a; tmp.end0b = spw.end0b; tmp.end1a = spw.end1a; tmp.end1b = spw.end1b;
+        std::vector<double> dltw(nw);
+        for (int j = 0; j < nw; ++j) {
+            dltw[j] = xw[j] - (tmp.x0 + j / tmp.inv_hx);
+            if (std::fabs(dltw[j] * tmp.inv_hx) > 1e-6) { err = p + "phase-shift template: the inner grid ps_k must be uniform in log10 k (geomspace)"; return false; }
+        }
+        const double kmin = klim.empty() ? kw[0] : klim[0], kmax = klim.empty() ? kw[nw - 1] : klim[1];
+        if (!(kmin > 0.) || !(kmax > kmin)) { err = p + "phase-shift template: ps_klim must satisfy 0 < kmin < kmax"; return false; }
+        std::vector<double> Mw;
+        dl_spline_moments_serial(wtab, spw, Mw);
+        std::vector<double> lds(dl_fs_shared_doubles(nw, 0), 0.);
+        DlFsShared sh = dl_fs_shared_carve(lds.data(), nw, 0);
+        for (int j = 0; j < nw; ++j) { sh.y[j] = wtab[j]; sh.M[j] = Mw[j]; }
+        tmp.ih = spw.ih.data(); tmp.x_t = xw.data(); tmp.dlt = dltw.data();
+        dl_fs_phase2d(0, 1, tmp, sh);
+        ps_tab.assign((size_t)DL_PS_HEAD + 2 * (size_t)d.n_t + 4 * (size_t)(nw - 1), 0.);
+        ps_tab[0] = kmin; ps_tab[1] = kmax; ps_tab[2] = tmp.x0; ps_tab[3] = tmp.inv_hx; ps_tab[4] = (double)(nw - 2);
+        for (int j = 0; j < d.n_t; ++j) { ps_tab[DL_PS_HEAD + 2 * (size_t)j] = k_t[j]; ps_tab[DL_PS_HEAD + 2 * (size_t)j + 1] = kshift[j]; }
+        double* coefw = ps_tab.data() + DL_PS_HEAD + 2 * (size_t)d.n_t;
+        for (int j = 0; j < nw - 1; ++j)
+            for (int q = 0; q < 4; ++q) coefw[(size_t)4 * j + q] = sh.coef[(size_t)(q >> 1) * 2 * nw + 2 * j + (q & 1)];
+    }
     // flexible BAO wiggles: kernel matrix K [n_ml, n_kin] and Legendre table [n_ell, n_mu] travel in the slots of the (otherwise unused) EFT matrices
     const bool flexible = d.theory == 2 && cfg.has_f64(p + "ml_matrix");
     std::vector<double> ml_tab;
@@ -663,7 +716,7 @@ inline bool dl_build_obs(const dl_config& cfg, int iobs, int n_params, DlObsHost
     oh.off_pass = arena.push(pass_tab);
     oh.off_png = arena.push(png_alpha);
     {
-        std::vector<double> band_tab = d.templ == 3 ? cfg.F(p + "band_templates") : std::vector<double>(2, 0.);
+        std::vector<double> band_tab = d.templ == 3 ? cfg.F(p + "band_templates") : d.templ == 4 ? ps_tab : std::vector<double>(2, 0.);   // (dl_ps_tab: the band template's pointer)
         oh.off_band = arena.push(band_tab);
     }
 

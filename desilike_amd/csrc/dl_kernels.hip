@@ -622,14 +622,29 @@ void dl_launch_fullshape_jac(const DlObsDev* obs_host, int n_obs, const DlObsDev
 // Workgroup size by batch (dl_bao_threads): ONE wave per point once the batch fills the chip (>= 4096 points: 16 resident workgroups per CU overlap each other's
 // per-mu chain and no wave waits at a barrier for another: 101 -> 86 us per 8192 points of the damped-BAO xi model, 70 -> 54 us for P_ell), 128 threads from 2048
 // points, 256 threads (the shortest life of a single point) below.  More threads than wavenumbers were tried: 320 / 384 threads per point, 146 us.
-template <int MODEL>
+// PS (phase-shift template, kind 4): instantiations of their own -- the point's wiggle spline is built in LDS between phases A and B (dl_bao_ps_*: knot values,
+// convolution, end corrections; every loop strides by the workgroup size, the end corrections need the 64 threads every size has) and phase B reads it instead of
+// o.coef_w.  The plain kernels keep their code, registers and LDS.
+template <int MODEL, bool PS = false>
 __global__ __launch_bounds__(512) void dl_bao_kernel(const DlObsDev o, const double* __restrict__ theta, int n_params, double* __restrict__ power, int64_t ld_power) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
     const double* th = theta + (size_t)b * n_params;
     dl_bao_phaseA(tid, nthr, o, th, lds);
+    if (PS) {
+        const DlPsShared ps = dl_bao_ps_carve(lds, o.n_t, o.n_in);
+        dl_bao_ps_knots(tid, nthr, o, th, ps);
+        __syncthreads();
+        dl_bao_ps_fir(tid, nthr, o, ps);
+        __syncthreads();
+        const double end = dl_bao_ps_end_moment(tid, o, ps);
+        __syncthreads();
+        dl_bao_ps_end_store(tid, o, ps, end);
+        __syncthreads();
+        dl_bao_ps_end_relations(tid, o, ps);
+    }
     __syncthreads();
-    dl_bao_phaseB_m<MODEL>(tid, nthr, o, lds);
+    dl_bao_phaseB_m<MODEL, PS>(tid, nthr, o, lds);
     __syncthreads();
     dl_store_with_pass(tid, nthr, o, th, lds + DL_BAO_PT, power + (size_t)b * (1 + o.n_var) * ld_power + o.col_offset);
 }
@@ -710,13 +725,20 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
             continue;
         }
         if (obs_host[i].theory == 2) {   // DL_THEORY_BAO_DAMPED
-            size_t shm = dl_bao_shared_doubles(obs_host[i].n_in) * sizeof(double);
+            const bool ps = obs_host[i].templ == 4;   // phase-shift template: per-point wiggle spline (33.0 KB more LDS at 2000 knots)
+            size_t shm = (ps ? dl_bao_ps_shared_doubles(obs_host[i].n_t, obs_host[i].n_in) : dl_bao_shared_doubles(obs_host[i].n_in)) * sizeof(double);
             auto launch_bao = [&](auto kernel) {
                 if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
                 DL_LAUNCH(kernel, dim3((unsigned)B), dim3((unsigned)dl_bao_threads(obs_host[i].n_kin, B)), shm, stream, obs_host[i], theta, n_params, power, ld_power);
             };
             const int model = obs_host[i].bao_mode >> 4;
-            if (model == 0) launch_bao(dl_bao_kernel<0>);
+            if (ps) {
+                if (model == 0) launch_bao(dl_bao_kernel<0, true>);
+                else if (model & 32) launch_bao(dl_bao_kernel<3, true>);
+                else if (model & 16) launch_bao(dl_bao_kernel<2, true>);
+                else launch_bao(dl_bao_kernel<1, true>);
+            }
+            else if (model == 0) launch_bao(dl_bao_kernel<0>);
             else if (model & 32) launch_bao(dl_bao_kernel<3>);
             else if (model & 16) launch_bao(dl_bao_kernel<2>);
             else launch_bao(dl_bao_kernel<1>);

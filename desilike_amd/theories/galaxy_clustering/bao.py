@@ -9,7 +9,8 @@ the broadband matrices, and for the correlation function the whole P_ell -> xi_e
 (:func:`desilike_amd.fftlog.hankel_operator`).  Broadband parameterisations: powers of k / s ('power', 'power3', 'even-power') and sums of
 mass-assignment-like kernels in Fourier space ('ngp', 'cic', 'tsc', 'pcs'; 'pcs2' for the correlation function), bao.py:468-523, 833-905 -- all
 constant matrices.  Wiggle models: 'standard' and the 'fix-damping' / 'move-all' / 'fog-damping' family of
-``DampedBAOWigglesPowerSpectrumMultipoles`` (bao.py:117-151); the Resummed / Flexible classes are not implemented.
+``DampedBAOWigglesPowerSpectrumMultipoles`` (bao.py:117-151), resummed and flexible wiggles.  Templates: ``BAOPowerSpectrumTemplate`` (constant wiggle spline) and
+``BAOPhaseShiftPowerSpectrumTemplate`` (``baoshift`` is one more kernel input: the wiggle spline is rebuilt per point).
 """
 import re
 
@@ -233,7 +234,8 @@ class _BaseDampedBAOTracer(BaseCalculator):
         spec = dict(theory=np.array([self._kind], dtype='i4'), nd=[1.], ells_in=np.array(self.ells, dtype='i4'), kin=self.kin, mu=self.mu, wmu_ell=self.wmu,
                     bao_mode=np.array([(1 if self.mode == 'reciso' else 0) | (self._model_bits << 4)], dtype='i4'), smoothing_radius=[self.smoothing_radius], pknow_dd_fid=template.pknow_dd_fid)
         spec.update(template._template_spec())
-        spec['template'] = np.array([0], dtype='i4')   # the BAO template never changes P(k) (power_template.py:372-376)
+        if template._kind != 4 or template.only_now:
+            spec['template'] = np.array([0], dtype='i4')   # the BAO template never changes P(k) (power_template.py:372-376); the phase-shift template moves the wiggles
         if self._resummed:
             spec['resummed'] = np.array([self.sigma_dd2, self.sigma_nl2, self.sigma_x2, self.shotnoise * self.sigma_sn2], dtype='f8')
         if self._flexible:
@@ -243,6 +245,7 @@ class _BaseDampedBAOTracer(BaseCalculator):
     def _input_map(self):
         toret = {name: name for name in ['qpar', 'qper', 'qiso', 'qap', 'df', 'dbeta', 'sigmas', 'sigmapar', 'sigmaper']}
         toret['b1X'] = toret['b1Y'] = 'b1'
+        if self.template._kind == 4 and not self.template.only_now: toret['baoshift'] = 'baoshift'
         if self._resummed: toret['dres'] = 'd'
         if self._flexible: toret['ml'] = list(self.wiggles_params)
         toret['pass'] = list(self._broadband_names)

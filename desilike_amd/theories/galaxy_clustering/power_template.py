@@ -97,6 +97,57 @@ class BAOPowerSpectrumTemplate(BasePowerSpectrumTemplate):
     _with_now_default = 'peakaverage'
 
 
+class BAOPhaseShiftPowerSpectrumTemplate(BAOPowerSpectrumTemplate):
+    r"""BAO template with the :math:`N_\mathrm{eff}`-induced phase shift of the wiggles (power_template.py:442-496; Baumann et al. 2018, arXiv:1803.10741):
+
+    .. math:: P_{dd}(k) = P_{now}^{fid}(k) + w\left(\mathrm{clip}(k + (\beta_\phi - 1)\, \Delta k(k))\right), \qquad
+              \Delta k(k) = \frac{\phi_\infty}{1 + (k_\star / k)^\epsilon} \frac{1}{r_d^{fid}},
+
+    with ``w`` the cubic interpolation in log10 k of the fiducial wiggles ``pk_dd - pknow_dd`` tabulated on ``geomspace(*klim_wiggles, 2000)`` and ``baoshift`` =
+    :math:`\beta_\phi`.  The per-point interpolation and the spline of its result run in the BAO theory kernel (csrc/dl_fullshape.h, ``dl_bao_ps_*``): BAO
+    wiggle theories only.
+
+    Parameters
+    ----------
+    phiinf, kstar, epsilon : float, default=0.227, 0.0324, 0.872
+        Best-fit values of eq. 3.3 of arXiv:1803.10741.
+    klim_wiggles : tuple, default=None
+        Ends ``(kmin, kmax)`` of the inner wiggle table, also the clip bounds of the shifted wavenumber.  The reference takes them from the cosmoprimo interpolator
+        (``extrap_kmin``, ``extrap_kmax``); default: the ends of a :class:`TabulatedFiducial`'s own table, (1e-5, 1e2) for :class:`SyntheticFiducial`.
+    """
+    _kind = 4  # DL_TEMPLATE_PHASESHIFT
+    _nk_wiggles = 2000   # power_template.py:490
+    _own_params = {'baoshift': dict(value=1., prior=dict(limits=[-8., 10.]), ref=dict(limits=[-8., 10.]), delta=8., latex=r'\beta_{\phi}')}   # power_template.yaml:174-216
+
+    def initialize(self):
+        if self._initialized:
+            return self
+        init = self.init
+        self.phiinf, self.kstar, self.epsilon = float(init.get('phiinf', 0.227)), float(init.get('kstar', 0.0324)), float(init.get('epsilon', 0.872))
+        super(BAOPhaseShiftPowerSpectrumTemplate, self).initialize()
+        rs_drag = getattr(self.fiducial, 'rs_drag', None)
+        if rs_drag is None:
+            self._initialized = False   # (set by the base class: a second call must raise again, not return a template without its tables)
+            raise ValueError('BAOPhaseShiftPowerSpectrumTemplate needs the sound horizon of the fiducial cosmology: pass rs_drag to TabulatedFiducial')
+        klim = init.get('klim_wiggles', None)
+        if klim is None:
+            table = getattr(self.fiducial, 'k', None)
+            klim = (1e-5, 1e2) if table is None else (float(table[0]), float(table[-1]))
+        self.klim_wiggles = (float(klim[0]), float(klim[1]))
+        self.kshift = self.phiinf / (1. + (self.kstar / self.k)**self.epsilon) / float(rs_drag)      # power_template.py:489
+        self.k_wiggles = np.geomspace(self.klim_wiggles[0], self.klim_wiggles[1], self._nk_wiggles)   # power_template.py:490
+        self.wiggles_fid = np.asarray(self.fiducial.pk_dd(self.k_wiggles), dtype='f8') - np.asarray(self.fiducial.pknow_dd(self.k_wiggles), dtype='f8')
+        return self
+
+    def _template_spec(self):
+        spec = super(BAOPhaseShiftPowerSpectrumTemplate, self)._template_spec()
+        if self.only_now:   # the wiggles are identically zero (power_template.py:493-495): the plain BAO template on the no-wiggle table
+            spec['template'] = np.array([0], dtype='i4')
+            return spec
+        spec.update(ps_kshift=self.kshift, ps_k=self.k_wiggles, ps_wiggles=self.wiggles_fid, ps_klim=np.array([self.k_wiggles[0], self.k_wiggles[-1]], dtype='f8'))
+        return spec
+
+
 class ShapeFitPowerSpectrumTemplate(BasePowerSpectrumTemplate):
     """ShapeFit template (power_template.py:696-764): ``pk_dd = pk_dd_fid exp(dm / a tanh(a ln(k / kp)) + dn ln(k / kp))``, ``f = f_fid df``."""
     _kind = 1  # DL_TEMPLATE_SHAPEFIT

@@ -57,6 +57,13 @@ typedef struct dl_ctx dl_ctx;         /* opaque; owns all persistent device cons
                                    * "kto_fid", "pkto_fid" (fiducial turn-over), inputs "in.m", "in.n", "in.qto", "in.dpto"; Kaiser-type theories */
 #define DL_TEMPLATE_BANDS     3   /* power_template.py:893-961: P_tt = P_tt_fid (1 + sum_i (dptt_i - 1) tent_i(k)), P_dd = P_tt / (f_fid df)^2; keys "band_templates" [n_band, n_t] (tent
                                    * functions at the template knots), "in.band" [n_band, 2] (theta column or -1, value); "pk_dd_fid" = P_tt_fid / f_fid^2; Kaiser-type theories */
+#define DL_TEMPLATE_PHASESHIFT 4  /* power_template.py:442-496 (BAO phase shift, arXiv:1803.10741): P_dd = P_now_fid + w(clip(k_t + (baoshift - 1) kshift_t, kmin, kmax)), w the not-a-knot
+                                   * cubic interpolation in log10 k of a constant inner wiggle table; BAO wiggle theories only (theory = 2).  Keys: "in.baoshift" f64[2] (theta column
+                                   * or -1, value; default 1), "ps_kshift" f64[n_t] (phiinf / (1 + (kstar / k_t)^epsilon) / rs_drag), "ps_k" f64[n_w] and "ps_wiggles" f64[n_w] (the
+                                   * inner grid, uniform in log10 k -- its origin log10 ps_k[0] and spacing are derived from it -- and the fiducial P_dd - P_now on it), "ps_klim"
+                                   * f64[2] (clip bounds of the shifted wavenumber; default: the ends of ps_k).  "k_t" must be uniform in log10 k to rounding (geomspace, >= 128
+                                   * knots): the per-point spline of the shifted wiggles is solved by a convolution.  dl_create refuses the kind on another theory, k_t that is
+                                   * not uniform, and an inner grid that is not uniform in log10 k. */
 #define DL_THEORY_KAISER      0   /* full_shape.py:488-500, 545-550 */
 #define DL_THEORY_EFT_KAISER  1   /* + counter / stochastic terms full_shape.py:628-634 */
 #define DL_THEORY_BAO_DAMPED  2   /* damped BAO wiggles, 'standard' model bao.py:117-140 (+ broadband terms as pass-through columns, bao.py:495-534, 881-905) */

@@ -24,7 +24,7 @@ import ctypes
 import numpy as np
 
 # enumerations of include/desilike_amd.h
-DL_TEMPLATE_FIXED, DL_TEMPLATE_SHAPEFIT, DL_TEMPLATE_TURNOVER, DL_TEMPLATE_BANDS = 0, 1, 2, 3
+DL_TEMPLATE_FIXED, DL_TEMPLATE_SHAPEFIT, DL_TEMPLATE_TURNOVER, DL_TEMPLATE_BANDS, DL_TEMPLATE_PHASESHIFT = 0, 1, 2, 3, 4
 DL_THEORY_KAISER, DL_THEORY_EFT_KAISER, DL_THEORY_BAO_DAMPED, DL_THEORY_EMULATED, DL_THEORY_TNS, DL_THEORY_PNG = 0, 1, 2, 3, 4, 5
 DL_APMODE = {'qparqper': 0, 'qiso': 1, 'qap': 2, 'qisoqap': 3}
 
@@ -533,7 +533,19 @@ def extract_config(likelihood):
             cfg[p + 'tns_fog'] = np.array([{'lorentzian': 0, 'gaussian': 1}[pt.options['fog']]], dtype='i4')
         turnover = template.__class__.__name__.startswith('TurnOver')      # power_template.py:1293-1340
         bands = template.__class__.__name__.startswith('BandVelocity')      # power_template.py:868-970
-        cfg[p + 'template'] = np.array([DL_TEMPLATE_BANDS if bands else DL_TEMPLATE_TURNOVER if turnover else DL_TEMPLATE_SHAPEFIT if shapefit and not bao else DL_TEMPLATE_FIXED], dtype='i4')
+        phaseshift = template.__class__.__name__.startswith('BAOPhaseShift') and not getattr(template, 'only_now', False)      # power_template.py:442-496
+        if phaseshift and not bao:
+            raise NotImplementedError('BAOPhaseShiftPowerSpectrumTemplate: BAO wiggle theories are covered')
+        cfg[p + 'template'] = np.array([DL_TEMPLATE_PHASESHIFT if phaseshift else DL_TEMPLATE_BANDS if bands else DL_TEMPLATE_TURNOVER if turnover else DL_TEMPLATE_SHAPEFIT if shapefit and not bao else DL_TEMPLATE_FIXED], dtype='i4')
+        if phaseshift:
+            # the constants of calculate (power_template.py:489-491): shift of each template knot per unit (baoshift - 1), the reference's own fiducial wiggles on its own
+            # 2000-point grid between the interpolator's extrapolation bounds, which are also the clip bounds of the shifted wavenumber
+            kt = np.asarray(template.k, dtype='f8')
+            interpolator = template.pk_dd_interpolator_fid
+            kw = np.geomspace(interpolator.extrap_kmin, interpolator.extrap_kmax, 2000)
+            cfg[p + 'ps_kshift'] = template.phiinf / (1.0 + (template.kstar / kt)**template.epsilon) / template.fiducial.rs_drag
+            cfg[p + 'ps_k'], cfg[p + 'ps_klim'] = kw, np.array([kw[0], kw[-1]], dtype='f8')
+            cfg[p + 'ps_wiggles'] = np.asarray(interpolator(kw), dtype='f8') - np.asarray(template.pknow_dd_interpolator_fid(kw), dtype='f8')
         if turnover: cfg[p + 'kto_fid'], cfg[p + 'pkto_fid'] = np.array([template.kTO_fid], dtype='f8'), np.array([template.pkTO_dd_fid], dtype='f8')
         cfg[p + 'apmode'] = np.array([_apmode(template)], dtype='i4')
         cfg[p + 'transform'] = np.array([1 if getattr(obs, 'transform', None) == 'cubic' else 0], dtype='i4')
@@ -652,6 +664,7 @@ def extract_config(likelihood):
             cfg[p + 'in.band'] = np.array([column(name, value_of(name, 1.)) for name in band_names], dtype='f8')
         if bao: defaults.update(dbeta=1., sigmas=0.)
         else: defaults.update(sn0=0.)
+        if phaseshift: defaults.update(baoshift=1.)
         if resummed: names.setdefault('dres', names.get('d', 'd')); defaults.update(dres=1.)      # (growth rescaling `d` of the resummed wiggles, bao.py:201: the key's name is dres)
         if xi and not bao: defaults.pop('sn0')                             # no stochastic parameter for correlation functions (full_shape.py:336-364)
         for key, default in defaults.items():

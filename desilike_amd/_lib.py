@@ -27,6 +27,8 @@ SYMBOLS = {
     'dl_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
     'dl_eval_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_batch_derived': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_sample_solved': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_logposterior': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_logposterior_grad': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_fisher': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -378,6 +380,42 @@ class Context(object):
         self._check(self._lib.dl_eval_batch_derived(self._handle, ctypes.c_void_p(theta.data_ptr()), B, ptr(loglike, torch.float64, (B,)), ptr(logprior, torch.float64, (B,)),
                                                     ptr(status, torch.int32, (B,)), ptr(solved, torch.float64, (B, self.n_solved)),
                                                     ptr(hessian, torch.float64, (B, self.n_solved, self.n_solved)), ctypes.c_void_p(stream)))
+
+    def sample_solved(self, theta, index0=0, size=1, seed=42, stream=None):
+        """Posterior draws of the analytically solved parameters at the points ``theta [B, n_params]`` (``dl_sample_solved``; samples/chain.py:229-263):
+        ``(solved [B, size, n_solved], loglike [B, size], logprior [B, size], status [B])`` -- the draws and the log-likelihood / log-prior corrected so that their sum
+        is the un-marginalised log-posterior at (theta, draw); NaN where ``status`` is not 0.  ``index0``: global index of the first point in its chain (a draw is a
+        pure function of (seed, index0 + row, draw, component)).  ``theta``: a device tensor (device tensors are returned, asynchronous on ``stream``) or an array
+        (arrays are returned).  Raises ``ValueError`` when the context has no analytically solved parameter, or for ``size < 1``."""
+        import torch
+        size, index0, seed = int(size), int(index0), int(seed) & 0xFFFFFFFFFFFFFFFF
+        if size < 1:
+            raise ValueError('sample_solved: size must be at least 1, found {:d}'.format(size))
+        if index0 < 0:
+            raise ValueError('sample_solved: index0 must not be negative')
+        if self.n_solved == 0:
+            raise ValueError('sample_solved: the context has no analytically solved parameter')
+        host = not torch.is_tensor(theta)
+        device = torch.device('cuda', self.device)
+        if host:
+            theta = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(theta), dtype='f8'), device=device)
+        if stream is None:
+            stream = torch.cuda.current_stream(device).cuda_stream
+        B, ns = theta.shape[0], self.n_solved
+        theta = self._device_theta(theta, stream)
+        solved = torch.empty((B, size, ns), dtype=torch.float64, device=device)
+        loglike, logprior = torch.empty((B, size), dtype=torch.float64, device=device), torch.empty((B, size), dtype=torch.float64, device=device)
+        status = torch.empty(B, dtype=torch.int32, device=device)
+        if B:
+            rc = self._lib.dl_sample_solved(self._handle, ctypes.c_void_p(theta.data_ptr()), B, index0, size, seed, ctypes.c_void_p(solved.data_ptr()),
+                                            ctypes.c_void_p(loglike.data_ptr()), ctypes.c_void_p(logprior.data_ptr()), ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(stream))
+            if rc == 2:
+                raise ValueError('sample_solved: the context has no analytically solved parameter')
+            self._check(rc)
+        if host:
+            torch.cuda.synchronize(device)
+            return tuple(t.cpu().numpy() for t in (solved, loglike, logprior, status))
+        return solved, loglike, logprior, status
 
     def eval_logposterior(self, theta, logposterior, status=None, stream=None):
         """``logposterior[B]`` = loglikelihood + logprior, -inf where the sampler would reject the point (samplers/base.py:185-191); torch tensors, asynchronous."""

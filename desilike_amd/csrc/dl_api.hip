@@ -14,6 +14,7 @@
 #include "dl_kernels.h"
 #include "dl_ens_fold.h"
 #include "dl_prior.h"
+#include "dl_sample_solved.h"
 
 static thread_local std::string g_last_error;
 void dl_set_last_error(const char* msg) { g_last_error = msg ? msg : ""; }
@@ -90,6 +91,11 @@ struct dl_ctx {
     double* eg_wt[3] = {nullptr, nullptr, nullptr};   // per MLP engine: its kernels transposed [out][in], packed (the backward pass)
     int eg_ngt = 0;
     int64_t eg_cap = 0;
+    // posterior draws of the solved parameters (dl_sample_solved): what the evaluation returns for the points of a pass -- solved [cap, n_solved], Hessian
+    // [cap, n_solved, n_solved], loglike [cap], logprior [cap], status [cap]
+    double *ss_solved = nullptr, *ss_hessian = nullptr, *ss_loglike = nullptr, *ss_logprior = nullptr;
+    int32_t* ss_status = nullptr;
+    int64_t ss_cap = 0;
     // the workspaces are shared by every call on this context: a call on another stream than the previous one waits for it (event recorded on the old stream
     // at the moment of the switch: calls that stay on one stream pay nothing)
     hipStream_t last_stream = nullptr;
@@ -497,6 +503,8 @@ void dl_destroy(dl_ctx* ctx) {
     for (double* p : {ctx->ej_basis, ctx->ej_u, ctx->ej_c, ctx->ej_dc, ctx->ej_resid, ctx->ej_rows}) if (p) (void)hipFree(p);
     for (double* p : {ctx->eg_gt, ctx->eg_u, ctx->eg_v, ctx->eg_q, ctx->eg_gb, ctx->eg_wt[0], ctx->eg_wt[1], ctx->eg_wt[2]}) if (p) (void)hipFree(p);
     if (ctx->grad_status) (void)hipFree(ctx->grad_status);
+    for (double* p : {ctx->ss_solved, ctx->ss_hessian, ctx->ss_loglike, ctx->ss_logprior}) if (p) (void)hipFree(p);
+    if (ctx->ss_status) (void)hipFree(ctx->ss_status);
     void* ptrs[] = {ctx->arena_dev, ctx->priors_dev, ctx->wt_white_dev, ctx->wt_frag_dev, ctx->bias_white_dev, ctx->wt_full_dev, ctx->bias_full_dev, ctx->wh_dev,
                     ctx->bias_wh_dev, ctx->flatdata_dev, ctx->transform_dev, ctx->tconst_dev, ctx->power_ws, ctx->delta_ws, ctx->flat_ws, ctx->stencil_ws, ctx->theta_stage, ctx->out_stage,
                     ctx->status_stage, ctx->gemm_counters, ctx->obs_array_dev};
@@ -738,6 +746,46 @@ int dl_eval_batch_derived(dl_ctx* ctx, const double* theta_dev, int64_t B, doubl
                           double* hessian_dev, void* hip_stream) {
     if (ctx && hessian_dev && ctx->n_solved == 0) return dl_fail(ctx, "dl_eval_batch_derived: no analytically solved parameter in this likelihood");
     return dl_eval_impl(ctx, theta_dev, B, loglike_dev, logprior_dev, nullptr, status_dev, solved_dev, hip_stream, 0, hessian_dev);
+}
+
+// Posterior draws of the analytically solved parameters (dl_sample_solved.h).  Per pass of DL_CHUNK points (the passes and the reserve policy of dl_eval_impl): the
+// launch sequence of dl_eval_batch_derived into workspaces of the context, then the draw kernel.
+int dl_sample_solved(dl_ctx* ctx, const double* theta_dev, int64_t B, int64_t index0, int32_t size, uint64_t seed, double* solved_dev, double* loglike_dev,
+                     double* logprior_dev, int32_t* status_dev, void* hip_stream) {
+    if (!ctx) { g_last_error = "dl_sample_solved: null context"; return 1; }
+    if (ctx->n_solved == 0) return 2;   // nothing to draw, nothing launched
+    if (B < 0 || (B > 0 && !theta_dev) || index0 < 0) return dl_fail(ctx, "dl_sample_solved: invalid batch");
+    if (size < 1) return dl_fail(ctx, "dl_sample_solved: size must be at least 1");
+    if (B > 0 && (!solved_dev || !loglike_dev || !logprior_dev)) return dl_fail(ctx, "dl_sample_solved: null output");
+    if (B == 0) return 0;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const int ns = ctx->n_solved, P = ctx->n_params;
+    const int64_t need = std::min<int64_t>(B, DL_CHUNK);
+    if (need > ctx->ss_cap) {
+        if (ctx->ss_cap > 0) DL_HIP_CHECK(ctx, hipDeviceSynchronize());   // (kernels of earlier calls may still use the buffers about to be freed)
+        for (double** p : {&ctx->ss_solved, &ctx->ss_hessian, &ctx->ss_loglike, &ctx->ss_logprior}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+        if (ctx->ss_status) { (void)hipFree(ctx->ss_status); ctx->ss_status = nullptr; }
+        ctx->ss_cap = 0;
+        const int64_t cap = std::min<int64_t>(std::max<int64_t>(need, 1024), DL_CHUNK);
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ss_solved, (size_t)cap * ns * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ss_hessian, (size_t)cap * ns * ns * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ss_loglike, (size_t)cap * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ss_logprior, (size_t)cap * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ss_status, (size_t)cap * sizeof(int32_t)));
+        DL_HIP_CHECK(ctx, hipDeviceSynchronize());
+        ctx->ss_cap = cap;
+    }
+    for (int64_t b0 = 0; b0 < B; b0 += DL_CHUNK) {
+        const int64_t nb = std::min<int64_t>(DL_CHUNK, B - b0);
+        if (dl_eval_impl(ctx, theta_dev + (size_t)b0 * P, nb, ctx->ss_loglike, ctx->ss_logprior, nullptr, ctx->ss_status, ctx->ss_solved, hip_stream, 0, ctx->ss_hessian))
+            return 1;
+        dl_launch_sample_solved(ctx->marg, ctx->ss_hessian, ctx->ss_solved, ctx->ss_loglike, ctx->ss_logprior, ctx->ss_status, nb, index0 + b0, size, seed,
+                                solved_dev + (size_t)b0 * size * ns, loglike_dev + (size_t)b0 * size, logprior_dev + (size_t)b0 * size,
+                                status_dev ? status_dev + b0 : nullptr, stream);
+    }
+    DL_HIP_CHECK(ctx, hipGetLastError());
+    return 0;
 }
 
 int dl_eval_logposterior(dl_ctx* ctx, const double* theta_dev, int64_t B, double* logposterior_dev, int32_t* status_dev, void* hip_stream) {

@@ -587,3 +587,8 @@ class Samples(dict):
         for value in self.values():
             return np.shape(value)
         return ()
+
+    def sample_solved(self, likelihood, size=1, seed=42):
+        """Sample the analytically marginalised parameters of ``likelihood`` at these samples (samples/chain.py:229-263): :func:`desilike_amd.solved.sample_solved`."""
+        from .solved import sample_solved
+        return sample_solved(likelihood, self, size=size, seed=seed)

@@ -162,10 +162,25 @@ int  dl_eval_batch(dl_ctx* ctx, const double* theta_dev, int64_t B,
                    int32_t* status_dev, double* solved_dev, void* hip_stream);
 
 /* dl_eval_batch plus the derived outputs the reference attaches to the log-likelihood of a marginalised fit (likelihoods/base.py:388-390, consumed by
- * Chain.sample_solved, samples/chain.py:229-263): hessian_dev[B, n_solved, n_solved] = second derivatives of the log-likelihood w.r.t. the analytically
+ * Chain.sample_solved, samples/chain.py:229-263, and by dl_sample_solved below): hessian_dev[B, n_solved, n_solved] = second derivatives of the log-likelihood w.r.t. the analytically
  * solved parameters, -T^T P T (the prior's part is the constant -diag(1 / scale^2) of marg.prior).  Any output may be NULL. */
 int  dl_eval_batch_derived(dl_ctx* ctx, const double* theta_dev, int64_t B, double* loglike_dev, double* logprior_dev, int32_t* status_dev,
                            double* solved_dev, double* hessian_dev, void* hip_stream);
+
+/* Posterior draws of the analytically solved parameters at the points of a chain (Chain.sample_solved, samples/chain.py:229-263; csrc/dl_sample_solved.h): per point
+ * the launch sequence of dl_eval_batch_derived into workspaces of the context (same passes, same reserve policy), then ONE kernel, one lane per point, that factorises
+ * A = -hessian + diag(1 / scale^2) = C C^T once and, for each of the ``size`` draws, takes v = C^-T z (z standard Gaussians; covariance A^-1) and x = solution + v.
+ *   solved_dev [B, size, n_solved] the draws x ('.marg' and '.best' parameters alike, as in the reference);
+ *   loglike_dev [B, size] = loglikelihood + 1/2 v.hessian.v + 1/2 logdet A[marg, marg] (the determinant over the '.marg' parameters only);
+ *   logprior_dev [B, size] = logprior - 1/2 sum_s v_s^2 / scale_s^2; their sum is the log-posterior at (theta, x) with NO parameter marginalised;
+ *   status_dev [B] (may be NULL): the status of the evaluation; a point whose status is not DL_STATUS_OK, or for which a pivot of A is not positive and finite --
+ *   reported as DL_STATUS_NONFINITE --, gets NaN draws and NaN values.
+ * Random draws: Philox4x32-10 keyed by ``seed``, counter (index lo, index hi, draw, 80 | pair << 8) with index = index0 + row: the global index of the point in the
+ * chain; Box-Muller pair ``pair`` gives components 2 pair and 2 pair + 1.  A draw is a pure function of (seed, index, draw, component): cutting a chain into calls
+ * (with the matching index0) or asking for fewer draws changes no bit.  size >= 1.  Returns 0; 1 on error; 2 -- nothing launched -- when the context has no
+ * analytically solved parameter.  Asynchronous on ``hip_stream``. */
+int  dl_sample_solved(dl_ctx* ctx, const double* theta_dev, int64_t B, int64_t index0, int32_t size, uint64_t seed, double* solved_dev, double* loglike_dev,
+                      double* logprior_dev, int32_t* status_dev, void* hip_stream);
 
 /* What a sampler consumes (BasePosteriorSampler.logposterior, desilike/samplers/base.py:144-200): logposterior_dev[B] = loglikelihood + logprior, and -inf
  * for points outside the prior, with NaN inputs or a non-finite likelihood (samplers/base.py:185-191); status_dev[B] optional.  One launch sequence, no

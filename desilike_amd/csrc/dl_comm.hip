@@ -14,6 +14,7 @@
 
 #include "../../include/desilike_amd.h"
 #include "dl_kernels.h"
+#include "dl_sampler_dev.h"   // dl_fail, DL_HIP_CHECK
 
 namespace {
 
@@ -38,11 +39,6 @@ struct RcclApi {
 RcclApi g_rccl;
 std::mutex g_rccl_mutex;
 
-int fail(const std::string& msg) {
-    dl_set_last_error(msg.c_str());
-    return 1;
-}
-
 // Load RCCL once.  Order: the explicit path, the copy already mapped into the process (RTLD_NOLOAD), the default search path, /opt/rocm/lib.
 int load_rccl(const char* path) {
     std::lock_guard<std::mutex> lock(g_rccl_mutex);
@@ -52,7 +48,7 @@ int load_rccl(const char* path) {
     if (path && *path) {
         h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
         used = path;
-        if (!h) return fail(std::string("dl_comm: cannot load ") + path + ": " + dlerror());
+        if (!h) return dl_fail(std::string("dl_comm: cannot load ") + path + ": " + dlerror());
     }
     const char* names[] = {"librccl.so.1", "librccl.so"};
     for (int pass = 0; pass < 2 && !h; ++pass)
@@ -61,13 +57,13 @@ int load_rccl(const char* path) {
             if (h) { used = name; break; }
         }
     if (!h) { h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_LOCAL); used = "/opt/rocm/lib/librccl.so.1"; }
-    if (!h) return fail("dl_comm: RCCL (librccl.so.1) not found: pass its path to dl_comm_unique_id / dl_comm_create");
+    if (!h) return dl_fail("dl_comm: RCCL (librccl.so.1) not found: pass its path to dl_comm_unique_id / dl_comm_create");
     RcclApi api;
     api.handle = h;
     api.path = used;
 #define DL_SYM(field, name)                                                     \
     *(void**)(&api.field) = dlsym(h, name);                                     \
-    if (!api.field) return fail(std::string("dl_comm: symbol ") + name + " missing in " + used);
+    if (!api.field) return dl_fail(std::string("dl_comm: symbol ") + name + " missing in " + used);
     DL_SYM(GetUniqueId, "ncclGetUniqueId")
     DL_SYM(CommInitRank, "ncclCommInitRank")
     DL_SYM(CommDestroy, "ncclCommDestroy")
@@ -82,7 +78,7 @@ int load_rccl(const char* path) {
 
 int check(int rc, const char* what) {
     if (rc == dlNcclSuccess) return 0;
-    return fail(std::string(what) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "RCCL error"));
+    return dl_fail(std::string(what) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "RCCL error"));
 }
 
 }  // namespace
@@ -95,7 +91,7 @@ struct dl_comm {
 extern "C" {
 
 int dl_comm_unique_id(char* id, const char* rccl_library_path) {
-    if (!id) return fail("dl_comm_unique_id: null argument");
+    if (!id) return dl_fail("dl_comm_unique_id: null argument");
     if (load_rccl(rccl_library_path)) return 1;
     dlNcclUniqueId uid;
     std::memset(&uid, 0, sizeof(uid));
@@ -105,14 +101,14 @@ int dl_comm_unique_id(char* id, const char* rccl_library_path) {
 }
 
 int dl_comm_create(dl_comm** out, int device, int rank, int world, const char* id, const char* rccl_library_path) {
-    if (!out || !id) return fail("dl_comm_create: null argument");
+    if (!out || !id) return dl_fail("dl_comm_create: null argument");
     *out = nullptr;
-    if (world < 1 || rank < 0 || rank >= world) return fail("dl_comm_create: rank / world out of range");
+    if (world < 1 || rank < 0 || rank >= world) return dl_fail("dl_comm_create: rank / world out of range");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("dl_comm_create: no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail("dl_comm_create: device ordinal out of range");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dl_fail("dl_comm_create: no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return dl_fail("dl_comm_create: device ordinal out of range");
     if (load_rccl(rccl_library_path)) return 1;
-    if (hipSetDevice(device) != hipSuccess) return fail("dl_comm_create: hipSetDevice failed");
+    if (hipSetDevice(device) != hipSuccess) return dl_fail("dl_comm_create: hipSetDevice failed");
     dlNcclUniqueId uid;
     std::memcpy(uid.internal, id, DL_COMM_ID_BYTES);
     dl_comm* comm = new dl_comm();
@@ -140,18 +136,18 @@ int64_t dl_comm_info(const dl_comm* comm, const char* key) {
 }
 
 int dl_comm_allgather_f64(dl_comm* comm, const double* send_dev, double* recv_dev, int64_t count, void* hip_stream) {
-    if (!comm || !comm->comm) return fail("dl_comm_allgather_f64: null communicator");
-    if (count < 0 || (count > 0 && (!send_dev || !recv_dev))) return fail("dl_comm_allgather_f64: invalid argument");
+    if (!comm || !comm->comm) return dl_fail("dl_comm_allgather_f64: null communicator");
+    if (count < 0 || (count > 0 && (!send_dev || !recv_dev))) return dl_fail("dl_comm_allgather_f64: invalid argument");
     if (count == 0) return 0;
-    if (hipSetDevice(comm->device) != hipSuccess) return fail("dl_comm_allgather_f64: hipSetDevice failed");
+    if (hipSetDevice(comm->device) != hipSuccess) return dl_fail("dl_comm_allgather_f64: hipSetDevice failed");
     return check(g_rccl.AllGather(send_dev, recv_dev, (size_t)count, dlNcclFloat64, comm->comm, (hipStream_t)hip_stream), "ncclAllGather");
 }
 
 int dl_comm_broadcast_f64(dl_comm* comm, double* buf_dev, int64_t count, int root, void* hip_stream) {
-    if (!comm || !comm->comm) return fail("dl_comm_broadcast_f64: null communicator");
-    if (count < 0 || (count > 0 && !buf_dev) || root < 0 || root >= comm->world) return fail("dl_comm_broadcast_f64: invalid argument");
+    if (!comm || !comm->comm) return dl_fail("dl_comm_broadcast_f64: null communicator");
+    if (count < 0 || (count > 0 && !buf_dev) || root < 0 || root >= comm->world) return dl_fail("dl_comm_broadcast_f64: invalid argument");
     if (count == 0) return 0;
-    if (hipSetDevice(comm->device) != hipSuccess) return fail("dl_comm_broadcast_f64: hipSetDevice failed");
+    if (hipSetDevice(comm->device) != hipSuccess) return dl_fail("dl_comm_broadcast_f64: hipSetDevice failed");
     return check(g_rccl.Broadcast(buf_dev, buf_dev, (size_t)count, dlNcclFloat64, root, comm->comm, (hipStream_t)hip_stream), "ncclBroadcast");
 }
 

@@ -18,6 +18,7 @@
 
 #include "../../include/desilike_amd.h"
 #include "dl_kernels.h"
+#include "dl_sampler_dev.h"   // dl_fail
 
 #define DL_COV_MAX_THEORIES 8
 #define DL_COV_MAX_ELLS 5
@@ -36,10 +37,6 @@ struct dl_cov {
     int32_t *cell_i = nullptr, *pt_i = nullptr, *sym = nullptr;
     double *cell_d = nullptr, *pt_d = nullptr, *gtab = nullptr;
 };
-
-namespace {
-int cov_fail(const std::string& msg) { dl_set_last_error(msg.c_str()); return 1; }
-}
 
 // cell_i [n_cells, 8]: row, col, theory 1, theory 2, index of the Legendre table, zero-lag flag, first point, number of points
 // cell_d [n_cells, 4]: prefactor, front, den, const;  pt_i [n_points, 2]: interval of k_q in the k grid of theory 1 / 2;  pt_d [n_points, 6]: (k_q - k_j, k_j+1 - k_j) for
@@ -113,22 +110,22 @@ void dl_cov_destroy(dl_cov* plan) {
 int dl_cov_create(dl_cov** out, int device, int32_t n, int32_t n_theories, const int32_t* n_ell, const int32_t* n_k, const int32_t* ell0, const double* shotnoise,
                   int64_t n_cells, const int32_t* cell_i, const double* cell_d, int64_t n_points, const int32_t* pt_i, const double* pt_d, int32_t n_gtab, const double* gtab,
                   int64_t n_sym, const int32_t* sym) {
-    if (!out) return cov_fail("dl_cov_create: null argument");
+    if (!out) return dl_fail("dl_cov_create: null argument");
     *out = nullptr;
     if (n < 1 || n_theories < 1 || n_theories > DL_COV_MAX_THEORIES || n_cells < 0 || n_points < 0 || n_gtab < 1 || !n_ell || !n_k || !ell0 || !shotnoise || !gtab)
-        return cov_fail("dl_cov_create: invalid argument");
+        return dl_fail("dl_cov_create: invalid argument");
     for (int t = 0; t < n_theories; ++t)
-        if (n_ell[t] < 1 || n_ell[t] > DL_COV_MAX_ELLS || n_k[t] < 2) return cov_fail("dl_cov_create: a theory needs 1 to 5 multipoles and at least 2 wavenumbers");
+        if (n_ell[t] < 1 || n_ell[t] > DL_COV_MAX_ELLS || n_k[t] < 2) return dl_fail("dl_cov_create: a theory needs 1 to 5 multipoles and at least 2 wavenumbers");
     for (int64_t c = 0; c < n_cells; ++c) {
         const int32_t* ci = cell_i + c * 8;
         if (ci[0] < 0 || ci[0] >= n || ci[1] < 0 || ci[1] >= n || ci[2] < 0 || ci[2] >= n_theories || ci[3] < 0 || ci[3] >= n_theories || ci[4] < 0 || ci[4] >= n_gtab ||
             ci[6] < 0 || ci[7] < 0 || (int64_t)ci[6] + ci[7] > n_points)
-            return cov_fail("dl_cov_create: cell " + std::to_string(c) + " out of range");
+            return dl_fail("dl_cov_create: cell " + std::to_string(c) + " out of range");
         for (int q = ci[6]; q < ci[6] + ci[7]; ++q)
             if (pt_i[2 * (size_t)q] < 0 || pt_i[2 * (size_t)q] > n_k[ci[2]] - 2 || pt_i[2 * (size_t)q + 1] < 0 || pt_i[2 * (size_t)q + 1] > n_k[ci[3]] - 2)
-                return cov_fail("dl_cov_create: interpolation interval out of range in cell " + std::to_string(c));
+                return dl_fail("dl_cov_create: interpolation interval out of range in cell " + std::to_string(c));
     }
-    for (int64_t e = 0; e < n_sym; ++e) if (sym[2 * e] < 0 || sym[2 * e] >= n || sym[2 * e + 1] < 0 || sym[2 * e + 1] >= n) return cov_fail("dl_cov_create: symmetrisation pair out of range");
+    for (int64_t e = 0; e < n_sym; ++e) if (sym[2 * e] < 0 || sym[2 * e] >= n || sym[2 * e + 1] < 0 || sym[2 * e + 1] >= n) return dl_fail("dl_cov_create: symmetrisation pair out of range");
     dl_cov* plan = new dl_cov();
     plan->device = device; plan->n = n; plan->n_theories = n_theories; plan->n_cells = n_cells; plan->n_points = n_points; plan->n_sym = n_sym;
     for (int t = 0; t < n_theories; ++t) { plan->n_ell[t] = n_ell[t]; plan->n_k[t] = n_k[t]; plan->ell0[t] = ell0[t]; plan->shotnoise[t] = shotnoise[t]; }
@@ -141,32 +138,32 @@ int dl_cov_create(dl_cov** out, int device, int32_t n, int32_t n_theories, const
         !upload((void**)&plan->pt_i, pt_i, (size_t)n_points * 2 * sizeof(int32_t)) || !upload((void**)&plan->pt_d, pt_d, (size_t)n_points * 6 * sizeof(double)) ||
         !upload((void**)&plan->gtab, gtab, (size_t)n_gtab * DL_COV_MAX_ELLS * DL_COV_MAX_ELLS * sizeof(double)) || !upload((void**)&plan->sym, sym, (size_t)n_sym * 2 * sizeof(int32_t))) {
         dl_cov_destroy(plan);
-        return cov_fail("dl_cov_create: device allocation / upload failed");
+        return dl_fail("dl_cov_create: device allocation / upload failed");
     }
     *out = plan;
     return 0;
 }
 
 int dl_cov_apply(dl_cov* plan, const double* const* power_dev, int64_t B, double* cov_dev, void* hip_stream) {
-    if (!plan || !power_dev || !cov_dev || B < 0) return cov_fail("dl_cov_apply: invalid argument");
+    if (!plan || !power_dev || !cov_dev || B < 0) return dl_fail("dl_cov_apply: invalid argument");
     if (B == 0) return 0;
-    if (B > 65535) return cov_fail("dl_cov_apply: at most 65535 parameter points per call");
+    if (B > 65535) return dl_fail("dl_cov_apply: at most 65535 parameter points per call");
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (hipSetDevice(plan->device) != hipSuccess) return cov_fail("dl_cov_apply: hipSetDevice failed");
+    if (hipSetDevice(plan->device) != hipSuccess) return dl_fail("dl_cov_apply: hipSetDevice failed");
     DlCovTheories th;
     for (int t = 0; t < DL_COV_MAX_THEORIES; ++t) {
         const bool live = t < plan->n_theories;
-        if (live && power_dev[t] == nullptr) return cov_fail("dl_cov_apply: null power array");
+        if (live && power_dev[t] == nullptr) return dl_fail("dl_cov_apply: null power array");
         th.power[t] = live ? power_dev[t] : nullptr; th.n_ell[t] = live ? plan->n_ell[t] : 0; th.n_k[t] = live ? plan->n_k[t] : 0; th.ell0[t] = live ? plan->ell0[t] : -1;
         th.shotnoise[t] = live ? plan->shotnoise[t] : 0.;
     }
-    if (hipMemsetAsync(cov_dev, 0, (size_t)B * plan->n * plan->n * sizeof(double), stream) != hipSuccess) return cov_fail("dl_cov_apply: hipMemsetAsync failed");
+    if (hipMemsetAsync(cov_dev, 0, (size_t)B * plan->n * plan->n * sizeof(double), stream) != hipSuccess) return dl_fail("dl_cov_apply: hipMemsetAsync failed");
     if (plan->n_cells > 0)
         hipLaunchKernelGGL(dl_cov_kernel, dim3((unsigned)((plan->n_cells + 255) / 256), (unsigned)B), dim3(256), 0, stream, th, plan->cell_i, plan->cell_d, plan->pt_i, plan->pt_d, plan->gtab,
                            plan->n_cells, plan->n, cov_dev);
     if (plan->n_sym > 0)
         hipLaunchKernelGGL(dl_cov_sym_kernel, dim3((unsigned)((plan->n_sym + 255) / 256), (unsigned)B), dim3(256), 0, stream, plan->sym, plan->n_sym, plan->n, cov_dev);
-    if (hipGetLastError() != hipSuccess) return cov_fail("dl_cov_apply: launch failed");
+    if (hipGetLastError() != hipSuccess) return dl_fail("dl_cov_apply: launch failed");
     return 0;
 }
 

@@ -21,22 +21,12 @@
 
 #include "../../include/desilike_amd.h"
 #include "dl_kernels.h"
+#include "dl_sampler_dev.h"   // dl_fail, DL_HIP_CHECK
 #include "dl_finalize_part.h"
 #include "dl_ens_fold.h"
 #include "dl_scalar_prefetch.h"
 
 namespace {
-
-int fail(const std::string& msg) {
-    dl_set_last_error(msg.c_str());
-    return 1;
-}
-
-#define DL_ENS_HIP(call)                                                                              \
-    do {                                                                                              \
-        hipError_t err__ = (call);                                                                    \
-        if (err__ != hipSuccess) return fail(std::string(#call) + ": " + hipGetErrorString(err__));   \
-    } while (0)
 
 #define DL_ENS_THREADS 1024   // one workgroup
 struct DlEnsArgs {
@@ -326,22 +316,22 @@ void dl_ensemble_destroy(dl_ensemble* ens) {
 }
 
 int dl_ensemble_create(dl_ensemble** out, dl_ctx* ctx, int32_t nwalkers, double a, uint64_t seed, double offset, dl_comm* comm) {
-    if (!out || !ctx) return fail("dl_ensemble_create: null argument");
+    if (!out || !ctx) return dl_fail("dl_ensemble_create: null argument");
     *out = nullptr;
     const int P = (int)dl_info(ctx, "n_params");
-    if (nwalkers < 2 || nwalkers % 2 || nwalkers > 8192) return fail("dl_ensemble_create: nwalkers must be even, in [2, 8192]");
-    if (!(a > 1.)) return fail("dl_ensemble_create: stretch parameter a must be > 1");
+    if (nwalkers < 2 || nwalkers % 2 || nwalkers > 8192) return dl_fail("dl_ensemble_create: nwalkers must be even, in [2, 8192]");
+    if (!(a > 1.)) return dl_fail("dl_ensemble_create: stretch parameter a must be > 1");
     dl_ensemble* ens = new dl_ensemble();
     ens->ctx = ctx; ens->comm = comm; ens->nw = nwalkers; ens->P = P; ens->a = a; ens->seed = seed; ens->offset = offset;
     ens->device = (int)dl_info(ctx, "device");
     if (comm) {
         ens->rank = (int)dl_comm_info(comm, "rank"); ens->world = (int)dl_comm_info(comm, "world");
-        if ((int)dl_comm_info(comm, "device") != ens->device) { delete ens; return fail("dl_ensemble_create: communicator and context live on different devices"); }
+        if ((int)dl_comm_info(comm, "device") != ens->device) { delete ens; return dl_fail("dl_ensemble_create: communicator and context live on different devices"); }
     }
     const int half = nwalkers / 2;
     ens->count = (half + ens->world - 1) / ens->world;
     const size_t half_pad = (size_t)ens->count * ens->world;
-    auto bail = [&](const std::string& msg) { dl_ensemble_destroy(ens); return fail(msg); };
+    auto bail = [&](const std::string& msg) { dl_ensemble_destroy(ens); return dl_fail(msg); };
     if (hipSetDevice(ens->device) != hipSuccess) return bail("dl_ensemble_create: hipSetDevice failed");
     if (hipMalloc((void**)&ens->coords, (size_t)nwalkers * P * sizeof(double)) != hipSuccess || hipMalloc((void**)&ens->logp, (size_t)nwalkers * sizeof(double)) != hipSuccess ||
         hipMalloc((void**)&ens->prop, half_pad * P * sizeof(double)) != hipSuccess || hipMalloc((void**)&ens->factors, half_pad * sizeof(double)) != hipSuccess ||
@@ -367,36 +357,36 @@ static int dl_ens_logposterior(dl_ensemble* ens, const double* theta_dev, int n,
 }
 
 int dl_ensemble_set_state(dl_ensemble* ens, const double* coords, const double* logposterior, void* hip_stream) {
-    if (!ens || !coords) return fail("dl_ensemble_set_state: null argument");
+    if (!ens || !coords) return dl_fail("dl_ensemble_set_state: null argument");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_ENS_HIP(hipSetDevice(ens->device));
-    DL_ENS_HIP(hipMemcpyAsync(ens->coords, coords, (size_t)ens->nw * ens->P * sizeof(double), hipMemcpyHostToDevice, stream));
-    if (logposterior) DL_ENS_HIP(hipMemcpyAsync(ens->logp, logposterior, (size_t)ens->nw * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_ENS_HIP(hipStreamSynchronize(stream));   // the host buffers may be pageable
+    DL_HIP_CHECK(hipSetDevice(ens->device));
+    DL_HIP_CHECK(hipMemcpyAsync(ens->coords, coords, (size_t)ens->nw * ens->P * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (logposterior) DL_HIP_CHECK(hipMemcpyAsync(ens->logp, logposterior, (size_t)ens->nw * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));   // the host buffers may be pageable
     ens->have_logp = logposterior != nullptr;
     return 0;
 }
 
 int dl_ensemble_run(dl_ensemble* ens, int64_t niterations, int32_t thin_by, double* chain_dev, double* chain_logp_dev, void* hip_stream) {
-    if (!ens) return fail("dl_ensemble_run: null ensemble");
-    if (niterations < 0 || thin_by < 1) return fail("dl_ensemble_run: invalid argument");
+    if (!ens) return dl_fail("dl_ensemble_run: null ensemble");
+    if (niterations < 0 || thin_by < 1) return dl_fail("dl_ensemble_run: invalid argument");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_ENS_HIP(hipSetDevice(ens->device));
+    DL_HIP_CHECK(hipSetDevice(ens->device));
     const int nw = ens->nw, P = ens->P, half = nw / 2;
     if (!ens->have_logp) {
         // log-posterior of the starting positions: two half-ensemble batches through the same sharded path
         for (int h = 0; h < 2; ++h) {
             if (dl_ens_logposterior(ens, ens->coords + (size_t)h * half * P, half, ens->newlp, stream)) return 1;
-            DL_ENS_HIP(hipMemcpyAsync(ens->logp + (size_t)h * half, ens->newlp, (size_t)half * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            DL_HIP_CHECK(hipMemcpyAsync(ens->logp + (size_t)h * half, ens->newlp, (size_t)half * sizeof(double), hipMemcpyDeviceToDevice, stream));
         }
         if (ens->offset != 0.) {
             // rare path (marginalised posteriors with a constant): add the offset on the host
             std::vector<double> tmp(nw);
-            DL_ENS_HIP(hipMemcpyAsync(tmp.data(), ens->logp, (size_t)nw * sizeof(double), hipMemcpyDeviceToHost, stream));
-            DL_ENS_HIP(hipStreamSynchronize(stream));
+            DL_HIP_CHECK(hipMemcpyAsync(tmp.data(), ens->logp, (size_t)nw * sizeof(double), hipMemcpyDeviceToHost, stream));
+            DL_HIP_CHECK(hipStreamSynchronize(stream));
             for (double& v : tmp) v = (v != v ? -__builtin_huge_val() : v) + ens->offset;
-            DL_ENS_HIP(hipMemcpyAsync(ens->logp, tmp.data(), (size_t)nw * sizeof(double), hipMemcpyHostToDevice, stream));
-            DL_ENS_HIP(hipStreamSynchronize(stream));
+            DL_HIP_CHECK(hipMemcpyAsync(ens->logp, tmp.data(), (size_t)nw * sizeof(double), hipMemcpyHostToDevice, stream));
+            DL_HIP_CHECK(hipStreamSynchronize(stream));
         }
         ens->have_logp = true;
     }
@@ -405,8 +395,8 @@ int dl_ensemble_run(dl_ensemble* ens, int64_t niterations, int32_t thin_by, doub
     std::memset(&s, 0, sizeof(s));
     static unsigned long long* stamps_dev = nullptr;   // DL_ENS_STAMPS=1: per-phase times of the step kernel, printed at the end of the run (synchronises)
     const bool stamps_on = dl_options().ens_stamps;
-    if (stamps_on && !stamps_dev) DL_ENS_HIP(hipMalloc((void**)&stamps_dev, 8 * sizeof(unsigned long long)));
-    if (stamps_on) DL_ENS_HIP(hipMemsetAsync(stamps_dev, 0, 8 * sizeof(unsigned long long), stream));
+    if (stamps_on && !stamps_dev) DL_HIP_CHECK(hipMalloc((void**)&stamps_dev, 8 * sizeof(unsigned long long)));
+    if (stamps_on) DL_HIP_CHECK(hipMemsetAsync(stamps_dev, 0, 8 * sizeof(unsigned long long), stream));
     s.stamps = stamps_on ? stamps_dev : nullptr;
     s.coords = ens->coords; s.logp = ens->logp; s.nacc = ens->nacc; s.prop = ens->prop; s.factors = ens->factors; s.newlp = ens->newlp;
     s.nw = nw; s.P = P; s.a = ens->a; s.offset = ens->offset;
@@ -443,7 +433,7 @@ int dl_ensemble_run(dl_ensemble* ens, int64_t niterations, int32_t thin_by, doub
     std::memset(&f, 0, sizeof(f));
     static unsigned long long* fold_stamps_dev = nullptr;   // DL_ENS_FOLD_STAMPS=1: phase times of the theory kernel's proposal prologue, printed at the end of the run (synchronises)
     const bool fold_stamps = folded && dl_options().ens_fold_stamps;
-    if (fold_stamps && !fold_stamps_dev) DL_ENS_HIP(hipMalloc((void**)&fold_stamps_dev, (size_t)8192 * 8 * sizeof(unsigned long long)));
+    if (fold_stamps && !fold_stamps_dev) DL_HIP_CHECK(hipMalloc((void**)&fold_stamps_dev, (size_t)8192 * 8 * sizeof(unsigned long long)));
     if (fold_stamps) f.stamps = fold_stamps_dev;
     if (folded) {
         f.nacc = ens->nacc; f.priors = ens->fold_priors; f.a = ens->a; f.offset = ens->offset;
@@ -463,7 +453,7 @@ int dl_ensemble_run(dl_ensemble* ens, int64_t niterations, int32_t thin_by, doub
                 const int rc = dl_internal_eval_fold(ens->ctx, f, half, ens->part2[h], stream);
                 if (rc == 1) return 1;
                 if (rc == 2) {
-                    if (f.pend.half >= 0) return fail("dl_ensemble_run: the context left the folded path in the middle of a run");
+                    if (f.pend.half >= 0) return dl_fail("dl_ensemble_run: the context left the folded path in the middle of a run");
                     ens->fold = 0; folded = false;      // (first half-step of the first run: nothing pending yet -- fall through to the three-launch sequence)
                 } else {
                     if (f.pend.half >= 0) { std::swap(ens->coords, ens->coords_alt); std::swap(ens->logp, ens->logp_alt); }   // the launch wrote the state after the pending accepts
@@ -493,18 +483,18 @@ int dl_ensemble_run(dl_ensemble* ens, int64_t niterations, int32_t thin_by, doub
     s.half_prop = -1;
     set_record();
     dl_ens_launch(s, stream);
-    DL_ENS_HIP(hipGetLastError());
+    DL_HIP_CHECK(hipGetLastError());
     if (stamps_on) {
         unsigned long long h[8];
-        DL_ENS_HIP(hipMemcpyAsync(h, stamps_dev, sizeof(h), hipMemcpyDeviceToHost, stream));
-        DL_ENS_HIP(hipStreamSynchronize(stream));
+        DL_HIP_CHECK(hipMemcpyAsync(h, stamps_dev, sizeof(h), hipMemcpyDeviceToHost, stream));
+        DL_HIP_CHECK(hipStreamSynchronize(stream));
         const double n = h[7] ? 100. * (double)h[7] : 1.;
         fprintf(stderr, "dl_ensemble_run: step kernel, us per launch over %llu launches: requests + landing %.2f, draws %.2f, barrier %.2f, accept %.2f, record + move %.2f\n", h[7], h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n);
     }
     if (fold_stamps) {
         std::vector<unsigned long long> h((size_t)half * 16);
-        DL_ENS_HIP(hipMemcpyAsync(h.data(), fold_stamps_dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-        DL_ENS_HIP(hipStreamSynchronize(stream));
+        DL_HIP_CHECK(hipMemcpyAsync(h.data(), fold_stamps_dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        DL_HIP_CHECK(hipStreamSynchronize(stream));
         double acc[6] = {0., 0., 0., 0., 0., 0.};
         for (int b = 0; b < half; ++b) for (int q = 0; q < 6; ++q) acc[q] += (double)(h[(size_t)b * 8 + q + 1] - h[(size_t)b * 8 + q]);
         fprintf(stderr, "dl_ensemble_run: theory kernel of the last half-step, mean shader-clock ticks per workgroup: kernarg prefetch %.0f, draw + splits %.0f, decisions (loads + sums) %.0f, theta %.0f, barrier %.0f, phases %.0f\n",
@@ -515,24 +505,24 @@ int dl_ensemble_run(dl_ensemble* ens, int64_t niterations, int32_t thin_by, doub
 }
 
 int dl_ensemble_get_state(dl_ensemble* ens, double* coords, double* logposterior, int64_t* naccepted, void* hip_stream) {
-    if (!ens) return fail("dl_ensemble_get_state: null ensemble");
+    if (!ens) return dl_fail("dl_ensemble_get_state: null ensemble");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_ENS_HIP(hipSetDevice(ens->device));
-    if (coords) DL_ENS_HIP(hipMemcpyAsync(coords, ens->coords, (size_t)ens->nw * ens->P * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (logposterior) DL_ENS_HIP(hipMemcpyAsync(logposterior, ens->logp, (size_t)ens->nw * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (naccepted) DL_ENS_HIP(hipMemcpyAsync(naccepted, ens->nacc, (size_t)ens->nw * sizeof(long long), hipMemcpyDeviceToHost, stream));
-    DL_ENS_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipSetDevice(ens->device));
+    if (coords) DL_HIP_CHECK(hipMemcpyAsync(coords, ens->coords, (size_t)ens->nw * ens->P * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (logposterior) DL_HIP_CHECK(hipMemcpyAsync(logposterior, ens->logp, (size_t)ens->nw * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (naccepted) DL_HIP_CHECK(hipMemcpyAsync(naccepted, ens->nacc, (size_t)ens->nw * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     return 0;
 }
 
 int dl_ensemble_set_counter(dl_ensemble* ens, int64_t iteration, const int64_t* naccepted, void* hip_stream) {
-    if (!ens) return fail("dl_ensemble_set_counter: null ensemble");
-    if (iteration < 0) return fail("dl_ensemble_set_counter: negative iteration");
+    if (!ens) return dl_fail("dl_ensemble_set_counter: null ensemble");
+    if (iteration < 0) return dl_fail("dl_ensemble_set_counter: negative iteration");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_ENS_HIP(hipSetDevice(ens->device));
+    DL_HIP_CHECK(hipSetDevice(ens->device));
     if (naccepted) {
-        DL_ENS_HIP(hipMemcpyAsync(ens->nacc, naccepted, (size_t)ens->nw * sizeof(long long), hipMemcpyHostToDevice, stream));
-        DL_ENS_HIP(hipStreamSynchronize(stream));   // the host buffer may be pageable
+        DL_HIP_CHECK(hipMemcpyAsync(ens->nacc, naccepted, (size_t)ens->nw * sizeof(long long), hipMemcpyHostToDevice, stream));
+        DL_HIP_CHECK(hipStreamSynchronize(stream));   // the host buffer may be pageable
     }
     ens->iteration = iteration;
     return 0;

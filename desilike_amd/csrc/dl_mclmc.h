@@ -92,8 +92,7 @@ DL_NUTS_HD bool dl_mclmc_integrator(int integrator, int32_t* nstage, double* cb,
 // standard Gaussian of component i of the draw of `stream` at step `it`
 DL_NUTS_HD double dl_mclmc_gauss(long long it, uint32_t chain, int i, uint32_t stream, uint32_t k0, uint32_t k1) {
     const DlPhilox r = dl_philox4x32((uint32_t)it, (uint32_t)((unsigned long long)it >> 32), chain, stream | ((uint32_t)(i >> 1) << 8), k0, k1);
-    const double rad = sqrt(-2. * log1p(-dl_uniform53(r.x[0], r.x[1]))), ang = 6.283185307179586 * dl_uniform53(r.x[2], r.x[3]);
-    return (i & 1) ? rad * sin(ang) : rad * cos(ang);
+    return dl_box_muller(r, i);
 }
 
 // out = A v (transpose = false) or A^T v

@@ -19,6 +19,7 @@
 
 #include "../../include/desilike_amd.h"
 #include "dl_kernels.h"
+#include "dl_sampler_dev.h"   // dl_fail, DL_HIP_CHECK
 #include "dl_mh.h"
 #include "dl_finalize_part.h"
 
@@ -46,17 +47,6 @@ struct dl_mh {
 };
 
 namespace {
-
-int fail(const std::string& msg) {
-    dl_set_last_error(msg.c_str());
-    return 1;
-}
-
-#define DL_MH_HIP(call)                                                                               \
-    do {                                                                                              \
-        hipError_t err__ = (call);                                                                    \
-        if (err__ != hipSuccess) return fail(std::string(#call) + ": " + hipGetErrorString(err__));   \
-    } while (0)
 
 struct DlMhArgs {
     const double *coords, *logp, *prop;  // state before this launch, pending proposals
@@ -275,27 +265,27 @@ void dl_mh_destroy(dl_mh* mh) {
 
 int dl_mh_create(dl_mh** out, dl_ctx* ctx, int32_t nchains, int32_t vectorize, const int32_t* chain_ids, const int32_t* order, const int32_t* blocks,
                  const int32_t* oversample, int32_t nblocks, double proposal_scale, uint64_t seed, double offset, int64_t max_tries) {
-    if (!out || !ctx || !blocks || nblocks < 1) return fail("dl_mh_create: null argument");
+    if (!out || !ctx || !blocks || nblocks < 1) return dl_fail("dl_mh_create: null argument");
     *out = nullptr;
     const int P = (int)dl_info(ctx, "n_params");
-    if (P < 1 || P > DL_MH_MAX_P) return fail("dl_mh_create: the sampler takes 1 .. 64 parameters");
-    if (nchains < 1 || vectorize < 1 || vectorize > DL_MH_MAX_V) return fail("dl_mh_create: nchains >= 1 and 1 <= vectorize <= 64");
-    if (!(proposal_scale > 0.) || max_tries < 1) return fail("dl_mh_create: proposal_scale and max_tries must be positive");
+    if (P < 1 || P > DL_MH_MAX_P) return dl_fail("dl_mh_create: the sampler takes 1 .. 64 parameters");
+    if (nchains < 1 || vectorize < 1 || vectorize > DL_MH_MAX_V) return dl_fail("dl_mh_create: nchains >= 1 and 1 <= vectorize <= 64");
+    if (!(proposal_scale > 0.) || max_tries < 1) return dl_fail("dl_mh_create: proposal_scale and max_tries must be positive");
     std::vector<int32_t> start(nblocks + 1, 0), reps(nblocks), rep_block;
     for (int ib = 0; ib < nblocks; ++ib) {
         const int o = oversample ? oversample[ib] : 1;
-        if (blocks[ib] < 1 || o < 1) return fail("dl_mh_create: block sizes and oversampling factors must be >= 1");
+        if (blocks[ib] < 1 || o < 1) return dl_fail("dl_mh_create: block sizes and oversampling factors must be >= 1");
         start[ib + 1] = start[ib] + blocks[ib];
         reps[ib] = blocks[ib] * o;
         rep_block.insert(rep_block.end(), (size_t)reps[ib], ib);      // mcmc.py:254: every parameter index of the block repeated `o` times
     }
-    if (start[nblocks] != P) return fail("dl_mh_create: the blocks must add up to the number of parameters");
-    if ((int)rep_block.size() > DL_MH_MAX_REP || nblocks > 64) return fail("dl_mh_create: too many blocks / cycler entries");
+    if (start[nblocks] != P) return dl_fail("dl_mh_create: the blocks must add up to the number of parameters");
+    if ((int)rep_block.size() > DL_MH_MAX_REP || nblocks > 64) return dl_fail("dl_mh_create: too many blocks / cycler entries");
     std::vector<int32_t> ord(P), ids(nchains);
     std::vector<char> seen(P, 0);
     for (int i = 0; i < P; ++i) {
         ord[i] = order ? order[i] : i;
-        if (ord[i] < 0 || ord[i] >= P || seen[ord[i]]) return fail("dl_mh_create: order must be a permutation of the parameters");
+        if (ord[i] < 0 || ord[i] >= P || seen[ord[i]]) return dl_fail("dl_mh_create: order must be a permutation of the parameters");
         seen[ord[i]] = 1;
     }
     for (int c = 0; c < nchains; ++c) ids[c] = chain_ids ? chain_ids[c] : c;
@@ -303,7 +293,7 @@ int dl_mh_create(dl_mh** out, dl_ctx* ctx, int32_t nchains, int32_t vectorize, c
     mh->ctx = ctx; mh->device = (int)dl_info(ctx, "device"); mh->C = nchains; mh->V = vectorize; mh->P = P; mh->nblocks = nblocks; mh->n_rep = (int)rep_block.size();
     mh->scale = proposal_scale; mh->seed = seed; mh->offset = offset; mh->max_tries = max_tries;
     mh->deferred = getenv("DL_MH_NO_DEFER") == nullptr;
-    auto bail = [&](const std::string& msg) { dl_mh_destroy(mh); return fail(msg); };
+    auto bail = [&](const std::string& msg) { dl_mh_destroy(mh); return dl_fail(msg); };
     if (hipSetDevice(mh->device) != hipSuccess) return bail("dl_mh_create: hipSetDevice failed");
     const size_t C = nchains, V = vectorize;
     bool ok = true;
@@ -332,68 +322,68 @@ int dl_mh_create(dl_mh** out, dl_ctx* ctx, int32_t nchains, int32_t vectorize, c
 }
 
 int dl_mh_set_covariance(dl_mh* mh, const double* cholesky, void* hip_stream) {
-    if (!mh || !cholesky) return fail("dl_mh_set_covariance: null argument");
+    if (!mh || !cholesky) return dl_fail("dl_mh_set_covariance: null argument");
     hipStream_t stream = (hipStream_t)hip_stream;
     const int P = mh->P;
     for (int i = 0; i < P; ++i) {
-        if (!(cholesky[(size_t)i * P + i] > 0.)) return fail("dl_mh_set_covariance: the Cholesky factor must have a positive diagonal");
+        if (!(cholesky[(size_t)i * P + i] > 0.)) return dl_fail("dl_mh_set_covariance: the Cholesky factor must have a positive diagonal");
         for (int j = 0; j < P; ++j) {
             const double v = cholesky[(size_t)i * P + j];
-            if (v != v || (j > i && v != 0.)) return fail("dl_mh_set_covariance: expected a finite lower-triangular factor [P, P] (sorted parameter order)");
+            if (v != v || (j > i && v != 0.)) return dl_fail("dl_mh_set_covariance: expected a finite lower-triangular factor [P, P] (sorted parameter order)");
         }
     }
-    DL_MH_HIP(hipSetDevice(mh->device));
-    DL_MH_HIP(hipMemcpyAsync(mh->L, cholesky, (size_t)P * P * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_MH_HIP(hipStreamSynchronize(stream));   // the host buffer may be pageable
+    DL_HIP_CHECK(hipSetDevice(mh->device));
+    DL_HIP_CHECK(hipMemcpyAsync(mh->L, cholesky, (size_t)P * P * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));   // the host buffer may be pageable
     mh->have_cov = true;
     return 0;
 }
 
 int dl_mh_set_state(dl_mh* mh, const double* coords, const double* logposterior, const int64_t* weight, const int64_t* naccepted, int64_t tries, void* hip_stream) {
-    if (!mh || !coords) return fail("dl_mh_set_state: null argument");
-    if (tries < 0) return fail("dl_mh_set_state: negative try counter");
+    if (!mh || !coords) return dl_fail("dl_mh_set_state: null argument");
+    if (tries < 0) return dl_fail("dl_mh_set_state: negative try counter");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_MH_HIP(hipSetDevice(mh->device));
+    DL_HIP_CHECK(hipSetDevice(mh->device));
     const size_t C = mh->C;
     std::vector<long long> w(C, 1), na(C, 0);
     if (weight) for (size_t c = 0; c < C; ++c) w[c] = weight[c];
     if (naccepted) for (size_t c = 0; c < C; ++c) na[c] = naccepted[c];
     const int d = mh->cur;
-    DL_MH_HIP(hipMemcpyAsync(mh->coords[d], coords, C * mh->P * sizeof(double), hipMemcpyHostToDevice, stream));
-    if (logposterior) DL_MH_HIP(hipMemcpyAsync(mh->logp[d], logposterior, C * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_MH_HIP(hipMemcpyAsync(mh->weight[d], w.data(), C * sizeof(long long), hipMemcpyHostToDevice, stream));
-    DL_MH_HIP(hipMemcpyAsync(mh->naccepted[d], na.data(), C * sizeof(long long), hipMemcpyHostToDevice, stream));
-    DL_MH_HIP(hipMemsetAsync(mh->fails[d], 0, C * sizeof(int32_t), stream));
-    DL_MH_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipMemcpyAsync(mh->coords[d], coords, C * mh->P * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (logposterior) DL_HIP_CHECK(hipMemcpyAsync(mh->logp[d], logposterior, C * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(mh->weight[d], w.data(), C * sizeof(long long), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(mh->naccepted[d], na.data(), C * sizeof(long long), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemsetAsync(mh->fails[d], 0, C * sizeof(int32_t), stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     mh->have_logp = logposterior != nullptr;
     mh->tries = tries;
     return 0;
 }
 
 int dl_mh_run(dl_mh* mh, int64_t ntries, int32_t thin_by, double* out_coords_dev, double* out_logp_dev, int64_t* out_weight_dev, int32_t* out_count_dev, void* hip_stream) {
-    if (!mh) return fail("dl_mh_run: null sampler");
-    if (ntries < 0 || thin_by < 1) return fail("dl_mh_run: invalid argument");
-    if (ntries > 0 && (!out_coords_dev || !out_logp_dev || !out_weight_dev || !out_count_dev)) return fail("dl_mh_run: the record buffers are required");
-    if (!mh->have_cov) return fail("dl_mh_run: no proposal covariance (dl_mh_set_covariance)");
-    if (ntries > 0x7fffffff) return fail("dl_mh_run: at most 2^31 - 1 tries per call");
+    if (!mh) return dl_fail("dl_mh_run: null sampler");
+    if (ntries < 0 || thin_by < 1) return dl_fail("dl_mh_run: invalid argument");
+    if (ntries > 0 && (!out_coords_dev || !out_logp_dev || !out_weight_dev || !out_count_dev)) return dl_fail("dl_mh_run: the record buffers are required");
+    if (!mh->have_cov) return dl_fail("dl_mh_run: no proposal covariance (dl_mh_set_covariance)");
+    if (ntries > 0x7fffffff) return dl_fail("dl_mh_run: at most 2^31 - 1 tries per call");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_MH_HIP(hipSetDevice(mh->device));
+    DL_HIP_CHECK(hipSetDevice(mh->device));
     const int C = mh->C, V = mh->V, P = mh->P;
     if (!mh->have_logp) {
         if (dl_eval_logposterior(mh->ctx, mh->coords[mh->cur], C, mh->logp[mh->cur], nullptr, stream)) return 1;
         std::vector<double> tmp(C);
-        DL_MH_HIP(hipMemcpyAsync(tmp.data(), mh->logp[mh->cur], (size_t)C * sizeof(double), hipMemcpyDeviceToHost, stream));
-        DL_MH_HIP(hipStreamSynchronize(stream));
+        DL_HIP_CHECK(hipMemcpyAsync(tmp.data(), mh->logp[mh->cur], (size_t)C * sizeof(double), hipMemcpyDeviceToHost, stream));
+        DL_HIP_CHECK(hipStreamSynchronize(stream));
         for (double& v : tmp) {
             v = (v != v ? -__builtin_huge_val() : v) + mh->offset;
-            if (!(v > -__builtin_huge_val())) return fail("dl_mh_run: the log-posterior of a starting position is not finite");
+            if (!(v > -__builtin_huge_val())) return dl_fail("dl_mh_run: the log-posterior of a starting position is not finite");
         }
-        DL_MH_HIP(hipMemcpyAsync(mh->logp[mh->cur], tmp.data(), (size_t)C * sizeof(double), hipMemcpyHostToDevice, stream));
-        DL_MH_HIP(hipStreamSynchronize(stream));
+        DL_HIP_CHECK(hipMemcpyAsync(mh->logp[mh->cur], tmp.data(), (size_t)C * sizeof(double), hipMemcpyHostToDevice, stream));
+        DL_HIP_CHECK(hipStreamSynchronize(stream));
         mh->have_logp = true;
     }
     if (ntries == 0) return 0;
-    DL_MH_HIP(hipMemsetAsync(out_count_dev, 0, (size_t)C * sizeof(int32_t), stream));
+    DL_HIP_CHECK(hipMemsetAsync(out_count_dev, 0, (size_t)C * sizeof(int32_t), stream));
     DlMhArgs s;
     std::memset(&s, 0, sizeof(s));
     s.newlp = mh->newlp; s.L = mh->L;
@@ -426,48 +416,48 @@ int dl_mh_run(dl_mh* mh, int64_t ntries, int32_t thin_by, double* out_coords_dev
     }
     s.try_prop = -1;
     launch();
-    DL_MH_HIP(hipGetLastError());
+    DL_HIP_CHECK(hipGetLastError());
     mh->tries += ntries;
     return 0;
 }
 
 int dl_mh_run_host(dl_mh* mh, int64_t ntries, int32_t thin_by, double* out_coords, double* out_logp, int64_t* out_weight, int32_t* out_count, void* hip_stream) {
-    if (!mh) return fail("dl_mh_run_host: null sampler");
-    if (ntries < 0 || (ntries > 0 && (!out_coords || !out_logp || !out_weight || !out_count))) return fail("dl_mh_run_host: invalid argument");
+    if (!mh) return dl_fail("dl_mh_run_host: null sampler");
+    if (ntries < 0 || (ntries > 0 && (!out_coords || !out_logp || !out_weight || !out_count))) return dl_fail("dl_mh_run_host: invalid argument");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_MH_HIP(hipSetDevice(mh->device));
+    DL_HIP_CHECK(hipSetDevice(mh->device));
     const size_t C = mh->C, P = mh->P;
     if (ntries > mh->rec_cap) {
-        DL_MH_HIP(hipStreamSynchronize(stream));
+        DL_HIP_CHECK(hipStreamSynchronize(stream));
         for (void* p : {(void*)mh->rec_coords, (void*)mh->rec_logp, (void*)mh->rec_weight, (void*)mh->rec_count}) if (p) (void)hipFree(p);
         mh->rec_coords = mh->rec_logp = nullptr; mh->rec_weight = nullptr; mh->rec_count = nullptr; mh->rec_cap = 0;
         if (hipMalloc((void**)&mh->rec_coords, C * ntries * P * sizeof(double)) != hipSuccess || hipMalloc((void**)&mh->rec_logp, C * ntries * sizeof(double)) != hipSuccess ||
             hipMalloc((void**)&mh->rec_weight, C * ntries * sizeof(long long)) != hipSuccess || hipMalloc((void**)&mh->rec_count, C * sizeof(int32_t)) != hipSuccess)
-            return fail("dl_mh_run_host: device allocation failed");
+            return dl_fail("dl_mh_run_host: device allocation failed");
         mh->rec_cap = ntries;
     }
     if (ntries == 0) return dl_mh_run(mh, 0, thin_by, nullptr, nullptr, nullptr, nullptr, hip_stream);
     if (dl_mh_run(mh, ntries, thin_by, mh->rec_coords, mh->rec_logp, reinterpret_cast<int64_t*>(mh->rec_weight), mh->rec_count, hip_stream)) return 1;
-    DL_MH_HIP(hipMemcpyAsync(out_coords, mh->rec_coords, C * ntries * P * sizeof(double), hipMemcpyDeviceToHost, stream));
-    DL_MH_HIP(hipMemcpyAsync(out_logp, mh->rec_logp, C * ntries * sizeof(double), hipMemcpyDeviceToHost, stream));
-    DL_MH_HIP(hipMemcpyAsync(out_weight, mh->rec_weight, C * ntries * sizeof(long long), hipMemcpyDeviceToHost, stream));
-    DL_MH_HIP(hipMemcpyAsync(out_count, mh->rec_count, C * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    DL_MH_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipMemcpyAsync(out_coords, mh->rec_coords, C * ntries * P * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(out_logp, mh->rec_logp, C * ntries * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(out_weight, mh->rec_weight, C * ntries * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(out_count, mh->rec_count, C * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     return 0;
 }
 
 int dl_mh_get_state(dl_mh* mh, double* coords, double* logposterior, int64_t* weight, int64_t* naccepted, int32_t* fails, void* hip_stream) {
-    if (!mh) return fail("dl_mh_get_state: null sampler");
+    if (!mh) return dl_fail("dl_mh_get_state: null sampler");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_MH_HIP(hipSetDevice(mh->device));
+    DL_HIP_CHECK(hipSetDevice(mh->device));
     const size_t C = mh->C;
     const int d = mh->cur;
-    if (coords) DL_MH_HIP(hipMemcpyAsync(coords, mh->coords[d], C * mh->P * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (logposterior) DL_MH_HIP(hipMemcpyAsync(logposterior, mh->logp[d], C * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (weight) DL_MH_HIP(hipMemcpyAsync(weight, mh->weight[d], C * sizeof(long long), hipMemcpyDeviceToHost, stream));
-    if (naccepted) DL_MH_HIP(hipMemcpyAsync(naccepted, mh->naccepted[d], C * sizeof(long long), hipMemcpyDeviceToHost, stream));
-    if (fails) DL_MH_HIP(hipMemcpyAsync(fails, mh->fails[d], C * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    DL_MH_HIP(hipStreamSynchronize(stream));
+    if (coords) DL_HIP_CHECK(hipMemcpyAsync(coords, mh->coords[d], C * mh->P * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (logposterior) DL_HIP_CHECK(hipMemcpyAsync(logposterior, mh->logp[d], C * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (weight) DL_HIP_CHECK(hipMemcpyAsync(weight, mh->weight[d], C * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    if (naccepted) DL_HIP_CHECK(hipMemcpyAsync(naccepted, mh->naccepted[d], C * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    if (fails) DL_HIP_CHECK(hipMemcpyAsync(fails, mh->fails[d], C * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     return 0;
 }
 

@@ -21,19 +21,9 @@
 
 #include "../../include/desilike_amd.h"
 #include "dl_kernels.h"
+#include "dl_sampler_dev.h"   // dl_fail, DL_HIP_CHECK
 
 namespace {
-
-int fail(const std::string& msg) {
-    dl_set_last_error(msg.c_str());
-    return 1;
-}
-
-#define DL_MLP_HIP(call)                                                                              \
-    do {                                                                                              \
-        hipError_t err__ = (call);                                                                    \
-        if (err__ != hipSuccess) return fail(std::string(#call) + ": " + hipGetErrorString(err__));   \
-    } while (0)
 
 typedef double dl_ml_double4 __attribute__((ext_vector_type(4)));
 
@@ -191,9 +181,9 @@ static int dl_mlp_reserve(dl_mlp* net, int64_t rows) {
     dl_mlp_free_ws(net);
     for (int l = 0; l < net->n_layers; ++l) {
         const size_t bytes = (size_t)rows * net->widths[l + 1] * sizeof(double);
-        DL_MLP_HIP(hipMalloc((void**)&net->z[l], bytes));
-        DL_MLP_HIP(hipMalloc((void**)&net->a[l], bytes));
-        DL_MLP_HIP(hipMalloc((void**)&net->delta[l], bytes));
+        DL_HIP_CHECK(hipMalloc((void**)&net->z[l], bytes));
+        DL_HIP_CHECK(hipMalloc((void**)&net->a[l], bytes));
+        DL_HIP_CHECK(hipMalloc((void**)&net->delta[l], bytes));
     }
     net->cap = rows;
     return 0;
@@ -222,17 +212,17 @@ void dl_mlp_destroy(dl_mlp* net) {
 }
 
 int dl_mlp_create(dl_mlp** out, int device, int32_t n_layers, const int32_t* widths, int32_t activation, const double* weights) {
-    if (!out || !widths || !weights) return fail("dl_mlp_create: null argument");
+    if (!out || !widths || !weights) return dl_fail("dl_mlp_create: null argument");
     *out = nullptr;
-    if (n_layers < 1 || n_layers > 16 || activation < 0 || activation > 2) return fail("dl_mlp_create: 1 to 16 layers, activation 0 (silu) / 1 (relu) / 2 (tanh)");
+    if (n_layers < 1 || n_layers > 16 || activation < 0 || activation > 2) return dl_fail("dl_mlp_create: 1 to 16 layers, activation 0 (silu) / 1 (relu) / 2 (tanh)");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("dl_mlp_create: no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail("dl_mlp_create: device ordinal out of range");
-    DL_MLP_HIP(hipSetDevice(device));
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dl_fail("dl_mlp_create: no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return dl_fail("dl_mlp_create: device ordinal out of range");
+    DL_HIP_CHECK(hipSetDevice(device));
     dl_mlp* net = new dl_mlp();
     net->device = device; net->n_layers = n_layers; net->act = activation;
     net->widths.assign(widths, widths + n_layers + 1);
-    for (int wdt : net->widths) if (wdt < 1) { delete net; return fail("dl_mlp_create: layer widths must be positive"); }
+    for (int wdt : net->widths) if (wdt < 1) { delete net; return dl_fail("dl_mlp_create: layer widths must be positive"); }
     int64_t off = 0;
     for (int l = 0; l < n_layers; ++l) {
         net->w_off.push_back(off); off += (int64_t)widths[l] * widths[l + 1];
@@ -241,7 +231,7 @@ int dl_mlp_create(dl_mlp** out, int device, int32_t n_layers, const int32_t* wid
     net->n_weights = off;
     net->z.assign(n_layers, nullptr); net->a.assign(n_layers, nullptr); net->delta.assign(n_layers, nullptr);
     const size_t bytes = (size_t)off * sizeof(double);
-    auto bail = [&](const std::string& msg) { dl_mlp_destroy(net); return fail(msg); };
+    auto bail = [&](const std::string& msg) { dl_mlp_destroy(net); return dl_fail(msg); };
     if (hipMalloc((void**)&net->w, bytes) != hipSuccess || hipMalloc((void**)&net->grad, bytes) != hipSuccess || hipMalloc((void**)&net->m, bytes) != hipSuccess ||
         hipMalloc((void**)&net->v, bytes) != hipSuccess || hipMalloc((void**)&net->partial, 1024 * sizeof(double)) != hipSuccess ||
         hipMalloc((void**)&net->loss, sizeof(double)) != hipSuccess)
@@ -265,22 +255,22 @@ int64_t dl_mlp_info(const dl_mlp* net, const char* key) {
 }
 
 int dl_mlp_get_weights(dl_mlp* net, double* weights, void* hip_stream) {
-    if (!net || !weights) return fail("dl_mlp_get_weights: null argument");
-    DL_MLP_HIP(hipSetDevice(net->device));
-    DL_MLP_HIP(hipMemcpyAsync(weights, net->w, (size_t)net->n_weights * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-    DL_MLP_HIP(hipStreamSynchronize((hipStream_t)hip_stream));
+    if (!net || !weights) return dl_fail("dl_mlp_get_weights: null argument");
+    DL_HIP_CHECK(hipSetDevice(net->device));
+    DL_HIP_CHECK(hipMemcpyAsync(weights, net->w, (size_t)net->n_weights * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
+    DL_HIP_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
     return 0;
 }
 
 int dl_mlp_forward(dl_mlp* net, const double* x_dev, int64_t rows, double* y_dev, void* hip_stream) {
-    if (!net || (rows > 0 && (!x_dev || !y_dev)) || rows < 0) return fail("dl_mlp_forward: invalid argument");
+    if (!net || (rows > 0 && (!x_dev || !y_dev)) || rows < 0) return dl_fail("dl_mlp_forward: invalid argument");
     if (rows == 0) return 0;
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_MLP_HIP(hipSetDevice(net->device));
+    DL_HIP_CHECK(hipSetDevice(net->device));
     if (dl_mlp_reserve(net, rows)) return 1;
     dl_mlp_forward_ws(net, x_dev, rows, stream);
-    DL_MLP_HIP(hipMemcpyAsync(y_dev, net->z[net->n_layers - 1], (size_t)rows * net->widths.back() * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    DL_MLP_HIP(hipGetLastError());
+    DL_HIP_CHECK(hipMemcpyAsync(y_dev, net->z[net->n_layers - 1], (size_t)rows * net->widths.back() * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    DL_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
@@ -305,29 +295,29 @@ static int dl_mlp_backprop(dl_mlp* net, const double* x, const double* y, int64_
 }
 
 int dl_mlp_loss_and_grad(dl_mlp* net, const double* x_dev, const double* y_dev, int64_t rows, double* loss_host, double* grad_host, void* hip_stream) {
-    if (!net || !x_dev || !y_dev || rows < 1) return fail("dl_mlp_loss_and_grad: invalid argument");
+    if (!net || !x_dev || !y_dev || rows < 1) return dl_fail("dl_mlp_loss_and_grad: invalid argument");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_MLP_HIP(hipSetDevice(net->device));
+    DL_HIP_CHECK(hipSetDevice(net->device));
     if (dl_mlp_reserve(net, rows)) return 1;
     if (dl_mlp_backprop(net, x_dev, y_dev, rows, stream)) return 1;
-    if (loss_host) DL_MLP_HIP(hipMemcpyAsync(loss_host, net->loss, sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (grad_host) DL_MLP_HIP(hipMemcpyAsync(grad_host, net->grad, (size_t)net->n_weights * sizeof(double), hipMemcpyDeviceToHost, stream));
-    DL_MLP_HIP(hipStreamSynchronize(stream));
-    DL_MLP_HIP(hipGetLastError());
+    if (loss_host) DL_HIP_CHECK(hipMemcpyAsync(loss_host, net->loss, sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (grad_host) DL_HIP_CHECK(hipMemcpyAsync(grad_host, net->grad, (size_t)net->n_weights * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 int dl_mlp_train(dl_mlp* net, const double* x_dev, const double* y_dev, int64_t n_samples, int64_t batch, int64_t n_steps, double lr, double beta1, double beta2, double eps,
                  double* loss_host, void* hip_stream) {
-    if (!net || !x_dev || !y_dev) return fail("dl_mlp_train: null argument");
-    if (n_samples < 1 || batch < 1 || batch > n_samples || n_steps < 0) return fail("dl_mlp_train: need 1 <= batch <= n_samples and n_steps >= 0");
+    if (!net || !x_dev || !y_dev) return dl_fail("dl_mlp_train: null argument");
+    if (n_samples < 1 || batch < 1 || batch > n_samples || n_steps < 0) return dl_fail("dl_mlp_train: need 1 <= batch <= n_samples and n_steps >= 0");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_MLP_HIP(hipSetDevice(net->device));
+    DL_HIP_CHECK(hipSetDevice(net->device));
     if (dl_mlp_reserve(net, batch)) return 1;
     const int n_in = net->widths.front(), n_out = net->widths.back();
     const int64_t chunks = n_samples / batch;      // batches are consecutive chunks of the sample set (the caller shuffles it); a remainder is not used
     double* loss_dev = nullptr;
-    if (loss_host && n_steps > 0) DL_MLP_HIP(hipMalloc((void**)&loss_dev, (size_t)n_steps * sizeof(double)));
+    if (loss_host && n_steps > 0) DL_HIP_CHECK(hipMalloc((void**)&loss_dev, (size_t)n_steps * sizeof(double)));
     for (int64_t it = 0; it < n_steps; ++it) {
         const int64_t c = (net->step % chunks);
         if (dl_mlp_backprop(net, x_dev + (size_t)c * batch * n_in, y_dev + (size_t)c * batch * n_out, batch, stream)) { if (loss_dev) (void)hipFree(loss_dev); return 1; }
@@ -341,9 +331,9 @@ int dl_mlp_train(dl_mlp* net, const double* x_dev, const double* y_dev, int64_t 
         hipError_t e = hipMemcpyAsync(loss_host, loss_dev, (size_t)n_steps * sizeof(double), hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         (void)hipFree(loss_dev);
-        if (e != hipSuccess) return fail(std::string("dl_mlp_train: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return dl_fail(std::string("dl_mlp_train: ") + hipGetErrorString(e));
     }
-    DL_MLP_HIP(hipGetLastError());
+    DL_HIP_CHECK(hipGetLastError());
     return 0;
 }
 

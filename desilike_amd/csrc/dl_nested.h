@@ -83,8 +83,7 @@ struct DlNestedArgs {
 // standard Gaussian of component i of the proposal of the replaced point of rank j
 DL_NUTS_HD double dl_nested_gauss(long long it, int sweep, uint32_t run, int j, int i, uint32_t k0, uint32_t k1) {
     const DlPhilox r = dl_philox4x32((uint32_t)it, (uint32_t)sweep, run, (uint32_t)DL_NESTED_STREAM_PROPOSE | ((uint32_t)(i >> 1) << 8) | ((uint32_t)j << 16), k0, k1);
-    const double rad = sqrt(-2. * log1p(-dl_uniform53(r.x[0], r.x[1]))), ang = 6.283185307179586 * dl_uniform53(r.x[2], r.x[3]);
-    return (i & 1) ? rad * sin(ang) : rad * cos(ang);
+    return dl_box_muller(r, i);
 }
 
 // log of the uniform of the Metropolis test of the replaced point of rank j (-inf for the uniform 0)

@@ -22,8 +22,10 @@
 #include <vector>
 
 #include "../../include/desilike_amd.h"
-#include "dl_kernels.h"   // dl_set_last_error
+#include "dl_sampler_dev.h"   // DlWave, DlBlock, dl_fail, DL_HIP_CHECK, dl_dev_alloc / free
 #include "dl_nested.h"
+
+static_assert(DL_NESTED_MAX_P == DL_SMC_MAX_P, "dl_pop_cholesky holds a DL_SMC_MAX_P square in LDS");
 
 #define DL_NESTED_WAVES 4    // points per workgroup of the seed, propose and accept kernels
 
@@ -45,54 +47,6 @@ struct dl_nested {
 };
 
 namespace {
-
-int fail(const std::string& msg) {
-    dl_set_last_error(msg.c_str());
-    return 1;
-}
-
-#define DL_NESTED_HIP(call)                                                                           \
-    do {                                                                                              \
-        hipError_t err__ = (call);                                                                    \
-        if (err__ != hipSuccess) return fail(std::string(#call) + ": " + hipGetErrorString(err__));   \
-    } while (0)
-
-// the device's component layout: lane = component
-struct DlNestedWave {
-    static constexpr int W = 1;
-    int P, lane;
-    __device__ int comp(int) const { return lane; }
-    __device__ bool on(int) const { return lane < P; }
-    __device__ double at(const double* x, int k) const { return __shfl(x[0], k, 64); }
-    __device__ void sync() const { __syncthreads(); }      // (the Cholesky kernel's workgroup is one wavefront)
-};
-
-// the DL_NESTED_THREADS threads of a run's workgroup: a wavefront's butterfly, then the wavefronts in index order
-struct DlNestedBlock {
-    int tid, n;
-    double* red;      // [2 * wavefronts] LDS
-    __device__ void sum2(double& a, double& b) const {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off, 64); b += __shfl_xor(b, off, 64); }
-        const int nw = n >> 6;
-        __syncthreads();      // (the previous reduction's reads)
-        if ((tid & 63) == 0) { red[2 * (tid >> 6)] = a; red[2 * (tid >> 6) + 1] = b; }
-        __syncthreads();
-        a = 0.; b = 0.;
-        for (int w = 0; w < nw; ++w) { a += red[2 * w]; b += red[2 * w + 1]; }
-    }
-    __device__ double max(double v) const {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-        const int nw = n >> 6;
-        __syncthreads();
-        if ((tid & 63) == 0) red[tid >> 6] = v;
-        __syncthreads();
-        v = red[0];
-        for (int w = 1; w < nw; ++w) v = fmax(v, red[w]);
-        return v;
-    }
-};
 
 __global__ __launch_bounds__(DL_NESTED_THREADS) void dl_nested_rank_kernel(DlNestedArgs a) {
     __shared__ uint64_t keys[DL_NESTED_MAX_N];
@@ -137,7 +91,7 @@ __global__ __launch_bounds__(DL_NESTED_THREADS) void dl_nested_rank_kernel(DlNes
     __syncthreads();
     dl_smc_scan_offsets(tid, T, M, cum, tot, gtot);
     __syncthreads();
-    const DlNestedBlock g{tid, T, red};
+    const DlBlock g{tid, T, red};
     const double logx = a.logx[k], logz = a.logz[k];
     DlNestedLevel t;
     dl_nested_evidence(g, L, slots, cum, N, M, logx, logz, &t);
@@ -151,43 +105,17 @@ __global__ __launch_bounds__(DL_NESTED_THREADS) void dl_nested_rank_kernel(DlNes
 }
 
 __global__ __launch_bounds__(64 * DL_SMC_MOMENT_WAVES) void dl_nested_moments_kernel(DlNestedArgs a) {
-    __shared__ double part[DL_SMC_MOMENT_WAVES][64];
-    const int k = blockIdx.x, row = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6, P = a.P;
+    const int k = blockIdx.x, row = blockIdx.y;
     if (!a.active[k]) return;      // (the whole workgroup)
-    const DlNestedWave l{P, lane};
     const int first = a.first[k], N = a.N - first;
-    const double *x = a.x + ((size_t)k * a.N + first) * P, *W = a.W + (size_t)k * a.N + first;
-    DlNutsVec<DlNestedWave> m, acc;
-    m.x[0] = 0.;
-    dl_smc_moment_partial(l, x, W, N, w, DL_SMC_MOMENT_WAVES, -1, m, 0., acc);
-    part[w][lane] = acc.x[0];
-    __syncthreads();
-    double s = 0.;
-    for (int v = 0; v < DL_SMC_MOMENT_WAVES; ++v) s += part[v][lane];
-    m.x[0] = s;
-    const double mrow = __shfl(s, row, 64);
-    __syncthreads();
-    dl_smc_moment_partial(l, x, W, N, w, DL_SMC_MOMENT_WAVES, row, m, mrow, acc);
-    part[w][lane] = acc.x[0];
-    __syncthreads();
-    if (w == 0 && lane < P) {
-        s = 0.;
-        for (int v = 0; v < DL_SMC_MOMENT_WAVES; ++v) s += part[v][lane];
-        if (lane <= row) a.cov[((size_t)k * P + row) * P + lane] = s;
-        if (row == 0) a.mean[(size_t)k * P + lane] = x[lane] + m.x[0];
-    }
+    const double *x = a.x + ((size_t)k * a.N + first) * a.P, *W = a.W + (size_t)k * a.N + first;
+    dl_pop_moments_row(a, x, W, N, k, row);
 }
 
 __global__ __launch_bounds__(64) void dl_nested_cholesky_kernel(DlNestedArgs a) {
-    __shared__ double C[DL_NESTED_MAX_P * DL_NESTED_MAX_P];
-    const int k = blockIdx.x, lane = threadIdx.x, P = a.P;
+    const int k = blockIdx.x, P = a.P;
     if (!a.active[k]) return;
-    const DlNestedWave l{P, lane};
-    for (int e = lane; e < P * P; e += 64) C[e] = 0.;
-    __syncthreads();
-    dl_smc_factor(l, a.cov + (size_t)k * P * P, a.widths, C);
-    double* out = a.chol + (size_t)k * P * P;
-    for (int e = lane; e < P * P; e += 64) out[e] = C[e];
+    dl_pop_cholesky(P, a.cov + (size_t)k * P * P, a.widths, a.chol + (size_t)k * P * P);
 }
 
 __global__ __launch_bounds__(64 * DL_NESTED_WAVES) void dl_nested_seed_kernel(DlNestedArgs a) {
@@ -196,12 +124,12 @@ __global__ __launch_bounds__(64 * DL_NESTED_WAVES) void dl_nested_seed_kernel(Dl
     if (r >= (long long)a.K * M) return;     // (whole wavefronts)
     const int k = (int)(r / M), j = (int)(r - (long long)k * M);
     if (!a.active[k]) return;
-    const DlNestedWave l{P, lane};
+    const DlWave l{P, lane};
     const int32_t* rank = a.rank + (size_t)k * N;
     const int dead = rank[j];
     const int src = rank[dl_nested_seed_rank(dl_nested_seed_uniform(a.iter[k], (uint32_t)a.sys_ids[k], j, a.k0, a.k1), N, M)];
     const size_t d = (size_t)k * N + dead, s = (size_t)k * N + src, rec = ((size_t)k * a.quota + a.out_count[k]) * M + j;
-    DlNutsVec<DlNestedWave> v;
+    DlNutsVec<DlWave> v;
     dl_nuts_load(l, v, a.x + d * P);
     dl_nuts_store(l, v, a.out_coords + rec * P);
     dl_nuts_load(l, v, a.x + s * P);
@@ -218,8 +146,8 @@ __global__ __launch_bounds__(64 * DL_NESTED_WAVES) void dl_nested_propose_kernel
     const long long r = (long long)blockIdx.x * DL_NESTED_WAVES + (threadIdx.x >> 6);
     if (r >= (long long)a.K * M) return;     // (whole wavefronts)
     const int k = (int)(r / M), j = (int)(r - (long long)k * M);
-    const DlNestedWave l{P, lane};
-    DlNutsVec<DlNestedWave> x, xp;
+    const DlWave l{P, lane};
+    DlNutsVec<DlWave> x, xp;
     dl_nuts_load(l, x, a.x + ((size_t)k * N + a.rank[(size_t)k * N + j]) * P);      // (a run at rest: the slot of its last iteration, or slot 0)
     if (!a.active[k]) {                      // its row is evaluated and ignored
         dl_nuts_store(l, x, a.prop + (size_t)r * P);
@@ -238,12 +166,12 @@ __global__ __launch_bounds__(64 * DL_NESTED_WAVES) void dl_nested_accept_kernel(
     if (r >= (long long)K * M) return;
     const int k = (int)(r / M), j = (int)(r - (long long)k * M);
     if (!a.active[k]) return;
-    const DlNestedWave l{P, lane};
+    const DlWave l{P, lane};
     const size_t d = (size_t)k * N + a.rank[(size_t)k * N + j];
     const double logu = dl_nested_log_uniform(a.iter[k], sweep, (uint32_t)a.sys_ids[k], j, a.k0, a.k1);
     const bool accept = dl_nested_accept(a.tmp[DL_NESTED_T_LSTAR * K + k], a.pi[d], a.Lp[r], a.pip[r], a.status[r], logu);
     if (accept) {
-        DlNutsVec<DlNestedWave> v;
+        DlNutsVec<DlWave> v;
         dl_nuts_load(l, v, a.prop + (size_t)r * P);
         dl_nuts_store(l, v, a.x + d * P);
     }
@@ -260,7 +188,7 @@ __global__ __launch_bounds__(DL_NESTED_THREADS) void dl_nested_finish_kernel(DlN
         if (tid == 0) a.out_mode[k] = a.mode[k];
         return;
     }
-    const DlNestedBlock g{tid, DL_NESTED_THREADS, red};
+    const DlBlock g{tid, DL_NESTED_THREADS, red};
     const double logx = a.logx[k], logz = a.logz[k];
     const double rem = dl_nested_remaining(g, a.L + (size_t)k * N, N, logx);
     if (tid != 0) return;
@@ -290,27 +218,17 @@ DlNestedArgs dl_nested_args(const dl_nested* m) {
     return a;
 }
 
-template <class T>
-bool dl_nested_alloc(T** p, size_t n) {
-    return hipMalloc((void**)p, n * sizeof(T)) == hipSuccess && hipMemset(*p, 0, n * sizeof(T)) == hipSuccess;
-}
-
-void dl_nested_free_sweeps(dl_nested* m) {
-    for (void** p : {(void**)&m->sscale, (void**)&m->acc, (void**)&m->flags})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-}
-
 // what dl_nested_set_live and dl_nested_set_state share: the scalars of the runs
 int dl_nested_check_live(const char* who, const dl_nested* m, const double* coords, const double* loglike, const double* logprior) {
     const size_t K = m->K, N = m->N, P = m->P;
     if (coords)
         for (size_t e = 0; e < K * N * P; ++e)
-            if (!std::isfinite(coords[e])) return fail(std::string(who) + ": the live points must be finite");
+            if (!std::isfinite(coords[e])) return dl_fail(std::string(who) + ": the live points must be finite");
     for (size_t e = 0; e < K * N; ++e) {
         if (!std::isfinite(logprior[e]))
-            return fail(std::string(who) + ": live point " + std::to_string(e % N) + " of run " + std::to_string(e / N) + " lies outside the prior (its log-prior is not finite)");
+            return dl_fail(std::string(who) + ": live point " + std::to_string(e % N) + " of run " + std::to_string(e / N) + " lies outside the prior (its log-prior is not finite)");
         if (!std::isfinite(loglike[e]))
-            return fail(std::string(who) + ": live point " + std::to_string(e % N) + " of run " + std::to_string(e / N) + " has no finite log-likelihood");
+            return dl_fail(std::string(who) + ": live point " + std::to_string(e % N) + " of run " + std::to_string(e / N) + " has no finite log-likelihood");
     }
     return 0;
 }
@@ -322,7 +240,7 @@ extern "C" {
 void dl_nested_destroy(dl_nested* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    dl_nested_free_sweeps(m);
+    dl_dev_free({(void**)&m->sscale, (void**)&m->acc, (void**)&m->flags});
     for (void* p : {(void*)m->x, (void*)m->L, (void*)m->pi, (void*)m->logx, (void*)m->logz, (void*)m->scale, (void*)m->W, (void*)m->logw, (void*)m->mean, (void*)m->cov,
                     (void*)m->chol, (void*)m->widths, (void*)m->tmp, (void*)m->prop, (void*)m->Lp, (void*)m->pip, (void*)m->sys_ids, (void*)m->mode, (void*)m->active,
                     (void*)m->rank, (void*)m->seeds, (void*)m->first, (void*)m->status, (void*)m->iter})
@@ -331,33 +249,33 @@ void dl_nested_destroy(dl_nested* m) {
 }
 
 int dl_nested_create(dl_nested** out, dl_ctx* ctx, int32_t nruns, int32_t nlive, const int32_t* run_ids, uint64_t seed, double offset, const double* widths) {
-    if (!out || !ctx || !widths) return fail("dl_nested_create: null argument");
+    if (!out || !ctx || !widths) return dl_fail("dl_nested_create: null argument");
     *out = nullptr;
     const int P = (int)dl_info(ctx, "n_params");
-    if (P < 1 || P > DL_NESTED_MAX_P) return fail("dl_nested_create: the sampler takes 1 .. 64 parameters, the context has " + std::to_string(P));
-    if (nruns < 1) return fail("dl_nested_create: nruns must be >= 1");
-    if (nlive < 64 || nlive > DL_NESTED_MAX_N || nlive % 64) return fail("dl_nested_create: nlive must be a multiple of 64 between 64 and 8192");
-    if (!std::isfinite(offset)) return fail("dl_nested_create: the offset must be finite");
+    if (P < 1 || P > DL_NESTED_MAX_P) return dl_fail("dl_nested_create: the sampler takes 1 .. 64 parameters, the context has " + std::to_string(P));
+    if (nruns < 1) return dl_fail("dl_nested_create: nruns must be >= 1");
+    if (nlive < 64 || nlive > DL_NESTED_MAX_N || nlive % 64) return dl_fail("dl_nested_create: nlive must be a multiple of 64 between 64 and 8192");
+    if (!std::isfinite(offset)) return dl_fail("dl_nested_create: the offset must be finite");
     std::vector<int32_t> ids(nruns);
     for (int k = 0; k < nruns; ++k) {
         ids[k] = run_ids ? run_ids[k] : k;
-        if (ids[k] < 0) return fail("dl_nested_create: run ids must be non-negative");
+        if (ids[k] < 0) return dl_fail("dl_nested_create: run ids must be non-negative");
     }
     for (int i = 0; i < P; ++i)
-        if (!(widths[i] > 0.) || !std::isfinite(widths[i])) return fail("dl_nested_create: the priors' widths must be positive and finite");
+        if (!(widths[i] > 0.) || !std::isfinite(widths[i])) return dl_fail("dl_nested_create: the priors' widths must be positive and finite");
     dl_nested* m = new dl_nested();
     m->ctx = ctx; m->device = (int)dl_info(ctx, "device"); m->K = nruns; m->N = nlive; m->P = P; m->seed = seed; m->offset = offset; m->ids = ids;
-    auto bail = [&](const std::string& msg) { dl_nested_destroy(m); return fail(msg); };
+    auto bail = [&](const std::string& msg) { dl_nested_destroy(m); return dl_fail(msg); };
     if (hipSetDevice(m->device) != hipSuccess) return bail("dl_nested_create: hipSetDevice failed");
     // (the arrays over the replaced points are sized for the largest ndelete, nlive / 2; Lp, pip and status for the nlive rows of dl_nested_set_live)
     const size_t K = nruns, N = nlive, p = P, M = N / 2;
-    const bool ok = dl_nested_alloc(&m->x, K * N * p) && dl_nested_alloc(&m->L, K * N) && dl_nested_alloc(&m->pi, K * N) && dl_nested_alloc(&m->logx, K) &&
-                    dl_nested_alloc(&m->logz, K) && dl_nested_alloc(&m->scale, K) && dl_nested_alloc(&m->W, K * N) && dl_nested_alloc(&m->logw, K * M) &&
-                    dl_nested_alloc(&m->mean, K * p) && dl_nested_alloc(&m->cov, K * p * p) && dl_nested_alloc(&m->chol, K * p * p) && dl_nested_alloc(&m->widths, p) &&
-                    dl_nested_alloc(&m->tmp, (size_t)DL_NESTED_NT * K) && dl_nested_alloc(&m->prop, K * M * p) && dl_nested_alloc(&m->Lp, K * N) &&
-                    dl_nested_alloc(&m->pip, K * N) && dl_nested_alloc(&m->sys_ids, K) && dl_nested_alloc(&m->mode, K) && dl_nested_alloc(&m->active, K) &&
-                    dl_nested_alloc(&m->rank, K * N) && dl_nested_alloc(&m->seeds, K * M) && dl_nested_alloc(&m->first, K) && dl_nested_alloc(&m->status, K * N) &&
-                    dl_nested_alloc(&m->iter, K);
+    const bool ok = dl_dev_alloc(&m->x, K * N * p) && dl_dev_alloc(&m->L, K * N) && dl_dev_alloc(&m->pi, K * N) && dl_dev_alloc(&m->logx, K) &&
+                    dl_dev_alloc(&m->logz, K) && dl_dev_alloc(&m->scale, K) && dl_dev_alloc(&m->W, K * N) && dl_dev_alloc(&m->logw, K * M) &&
+                    dl_dev_alloc(&m->mean, K * p) && dl_dev_alloc(&m->cov, K * p * p) && dl_dev_alloc(&m->chol, K * p * p) && dl_dev_alloc(&m->widths, p) &&
+                    dl_dev_alloc(&m->tmp, (size_t)DL_NESTED_NT * K) && dl_dev_alloc(&m->prop, K * M * p) && dl_dev_alloc(&m->Lp, K * N) &&
+                    dl_dev_alloc(&m->pip, K * N) && dl_dev_alloc(&m->sys_ids, K) && dl_dev_alloc(&m->mode, K) && dl_dev_alloc(&m->active, K) &&
+                    dl_dev_alloc(&m->rank, K * N) && dl_dev_alloc(&m->seeds, K * M) && dl_dev_alloc(&m->first, K) && dl_dev_alloc(&m->status, K * N) &&
+                    dl_dev_alloc(&m->iter, K);
     if (!ok) return bail("dl_nested_create: device allocation failed");
     if (!(hipMemcpy(m->sys_ids, ids.data(), K * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess &&
           hipMemcpy(m->widths, widths, p * sizeof(double), hipMemcpyHostToDevice) == hipSuccess && hipDeviceSynchronize() == hipSuccess))
@@ -367,58 +285,58 @@ int dl_nested_create(dl_nested** out, dl_ctx* ctx, int32_t nruns, int32_t nlive,
 }
 
 int dl_nested_set_hyper(dl_nested* m, int32_t ndelete, int32_t n_steps, double target_acceptance, double dlogz, double scale, void* hip_stream) {
-    if (!m) return fail("dl_nested_set_hyper: null sampler");
-    if (ndelete < 1 || ndelete > m->N / 2) return fail("dl_nested_set_hyper: ndelete must lie in 1 .. nlive / 2");
-    if (n_steps < 1 || n_steps > DL_NESTED_MAX_STEPS) return fail("dl_nested_set_hyper: n_steps must lie in 1 .. 1024");
-    if (!(target_acceptance > 0.) || !(target_acceptance < 1.)) return fail("dl_nested_set_hyper: target_acceptance must lie in (0, 1)");
-    if (!(dlogz > 0.) || !(dlogz < 1.)) return fail("dl_nested_set_hyper: dlogz must lie in (0, 1)");
-    if (!(scale >= 1e-3) || !(scale <= 1e3)) return fail("dl_nested_set_hyper: scale must lie in 1e-3 .. 1e3");
+    if (!m) return dl_fail("dl_nested_set_hyper: null sampler");
+    if (ndelete < 1 || ndelete > m->N / 2) return dl_fail("dl_nested_set_hyper: ndelete must lie in 1 .. nlive / 2");
+    if (n_steps < 1 || n_steps > DL_NESTED_MAX_STEPS) return dl_fail("dl_nested_set_hyper: n_steps must lie in 1 .. 1024");
+    if (!(target_acceptance > 0.) || !(target_acceptance < 1.)) return dl_fail("dl_nested_set_hyper: target_acceptance must lie in (0, 1)");
+    if (!(dlogz > 0.) || !(dlogz < 1.)) return dl_fail("dl_nested_set_hyper: dlogz must lie in (0, 1)");
+    if (!(scale >= 1e-3) || !(scale <= 1e3)) return dl_fail("dl_nested_set_hyper: scale must lie in 1e-3 .. 1e3");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_NESTED_HIP(hipSetDevice(m->device));
+    DL_HIP_CHECK(hipSetDevice(m->device));
     const size_t K = m->K, M = m->N / 2;
     if (n_steps != m->n_steps) {
-        DL_NESTED_HIP(hipDeviceSynchronize());      // kernels of earlier calls may still use the buffers about to be freed
-        dl_nested_free_sweeps(m);
+        DL_HIP_CHECK(hipDeviceSynchronize());      // kernels of earlier calls may still use the buffers about to be freed
+        dl_dev_free({(void**)&m->sscale, (void**)&m->acc, (void**)&m->flags});
         m->n_steps = 0;
-        if (!(dl_nested_alloc(&m->sscale, K * n_steps) && dl_nested_alloc(&m->acc, K * n_steps) && dl_nested_alloc(&m->flags, K * n_steps * M)))
-            return fail("dl_nested_set_hyper: device allocation failed");
-        DL_NESTED_HIP(hipDeviceSynchronize());
+        if (!(dl_dev_alloc(&m->sscale, K * n_steps) && dl_dev_alloc(&m->acc, K * n_steps) && dl_dev_alloc(&m->flags, K * n_steps * M)))
+            return dl_fail("dl_nested_set_hyper: device allocation failed");
+        DL_HIP_CHECK(hipDeviceSynchronize());
         m->n_steps = n_steps;
     }
     std::vector<double> s(K, scale);
-    DL_NESTED_HIP(hipMemcpyAsync(m->scale, s.data(), K * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_NESTED_HIP(hipStreamSynchronize(stream));   // the host buffer is pageable
+    DL_HIP_CHECK(hipMemcpyAsync(m->scale, s.data(), K * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));   // the host buffer is pageable
     m->M = ndelete; m->target_acceptance = target_acceptance; m->dlogz = dlogz;
     m->have_hyper = true;
     return 0;
 }
 
 int dl_nested_set_live(dl_nested* m, const double* coords, void* hip_stream) {
-    if (!m || !coords) return fail("dl_nested_set_live: null argument");
+    if (!m || !coords) return dl_fail("dl_nested_set_live: null argument");
     hipStream_t stream = (hipStream_t)hip_stream;
     const size_t K = m->K, N = m->N, P = m->P;
     for (size_t e = 0; e < K * N * P; ++e)
-        if (!std::isfinite(coords[e])) return fail("dl_nested_set_live: the live points must be finite");
+        if (!std::isfinite(coords[e])) return dl_fail("dl_nested_set_live: the live points must be finite");
     m->have_state = false;
-    DL_NESTED_HIP(hipSetDevice(m->device));
-    DL_NESTED_HIP(hipMemcpyAsync(m->x, coords, K * N * P * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipSetDevice(m->device));
+    DL_HIP_CHECK(hipMemcpyAsync(m->x, coords, K * N * P * sizeof(double), hipMemcpyHostToDevice, stream));
     if (dl_eval_batch(m->ctx, m->x, (int64_t)(K * N), m->L, m->pi, nullptr, m->status, nullptr, stream)) return 1;
     std::vector<double> L(K * N), pi(K * N), logz(K, -HUGE_VAL);
     std::vector<int32_t> status(K * N), mode(K, DL_NESTED_CLIMB);
-    DL_NESTED_HIP(hipMemcpyAsync(L.data(), m->L, K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
-    DL_NESTED_HIP(hipMemcpyAsync(pi.data(), m->pi, K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
-    DL_NESTED_HIP(hipMemcpyAsync(status.data(), m->status, K * N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    DL_NESTED_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipMemcpyAsync(L.data(), m->L, K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(pi.data(), m->pi, K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(status.data(), m->status, K * N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     m->evaluations += (int64_t)(K * N);
     for (size_t e = 0; e < K * N; ++e)
         if (status[e] != 0) L[e] = -HUGE_VAL;
     if (dl_nested_check_live("dl_nested_set_live", m, nullptr, L.data(), pi.data())) return 1;
-    DL_NESTED_HIP(hipMemsetAsync(m->logx, 0, K * sizeof(double), stream));
-    DL_NESTED_HIP(hipMemcpyAsync(m->logz, logz.data(), K * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_NESTED_HIP(hipMemcpyAsync(m->mode, mode.data(), K * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    DL_NESTED_HIP(hipMemsetAsync(m->iter, 0, K * sizeof(long long), stream));
-    DL_NESTED_HIP(hipMemsetAsync(m->rank, 0, K * N * sizeof(int32_t), stream));
-    DL_NESTED_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipMemsetAsync(m->logx, 0, K * sizeof(double), stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->logz, logz.data(), K * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->mode, mode.data(), K * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemsetAsync(m->iter, 0, K * sizeof(long long), stream));
+    DL_HIP_CHECK(hipMemsetAsync(m->rank, 0, K * N * sizeof(int32_t), stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     m->iterations = 0;
     m->have_state = true;
     return 0;
@@ -426,32 +344,32 @@ int dl_nested_set_live(dl_nested* m, const double* coords, void* hip_stream) {
 
 int dl_nested_set_state(dl_nested* m, const double* coords, const double* loglike, const double* logprior, const double* logx, const double* logz, const int64_t* counters,
                         const double* scale, const int32_t* modes, void* hip_stream) {
-    if (!m || !coords || !loglike || !logprior || !logx || !logz || !counters || !scale || !modes) return fail("dl_nested_set_state: null argument");
+    if (!m || !coords || !loglike || !logprior || !logx || !logz || !counters || !scale || !modes) return dl_fail("dl_nested_set_state: null argument");
     hipStream_t stream = (hipStream_t)hip_stream;
     const size_t K = m->K, N = m->N, P = m->P;
     std::vector<long long> it(K);
     for (size_t k = 0; k < K; ++k) {
-        if (!(logx[k] <= 0.) || !std::isfinite(logx[k])) return fail("dl_nested_set_state: logx must be finite and not above 0");
-        if (std::isnan(logz[k]) || logz[k] == HUGE_VAL) return fail("dl_nested_set_state: logz must be finite or -inf");
-        if (counters[k] < 0) return fail("dl_nested_set_state: negative iteration counter");
-        if (!(scale[k] >= 1e-3) || !(scale[k] <= 1e3)) return fail("dl_nested_set_state: scale must lie in 1e-3 .. 1e3");
-        if (modes[k] != DL_NESTED_REST && modes[k] != DL_NESTED_CLIMB) return fail("dl_nested_set_state: a mode is 0 (at rest) or 1 (climbing)");
+        if (!(logx[k] <= 0.) || !std::isfinite(logx[k])) return dl_fail("dl_nested_set_state: logx must be finite and not above 0");
+        if (std::isnan(logz[k]) || logz[k] == HUGE_VAL) return dl_fail("dl_nested_set_state: logz must be finite or -inf");
+        if (counters[k] < 0) return dl_fail("dl_nested_set_state: negative iteration counter");
+        if (!(scale[k] >= 1e-3) || !(scale[k] <= 1e3)) return dl_fail("dl_nested_set_state: scale must lie in 1e-3 .. 1e3");
+        if (modes[k] != DL_NESTED_REST && modes[k] != DL_NESTED_CLIMB) return dl_fail("dl_nested_set_state: a mode is 0 (at rest) or 1 (climbing)");
         it[k] = counters[k];
     }
     if (dl_nested_check_live("dl_nested_set_state", m, coords, loglike, logprior)) return 1;
-    DL_NESTED_HIP(hipSetDevice(m->device));
-    DL_NESTED_HIP(hipMemcpyAsync(m->x, coords, K * N * P * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_NESTED_HIP(hipMemcpyAsync(m->L, loglike, K * N * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_NESTED_HIP(hipMemcpyAsync(m->pi, logprior, K * N * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_NESTED_HIP(hipMemcpyAsync(m->logx, logx, K * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_NESTED_HIP(hipMemcpyAsync(m->logz, logz, K * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_NESTED_HIP(hipMemcpyAsync(m->iter, it.data(), K * sizeof(long long), hipMemcpyHostToDevice, stream));
-    DL_NESTED_HIP(hipMemcpyAsync(m->scale, scale, K * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_NESTED_HIP(hipMemcpyAsync(m->mode, modes, K * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    DL_NESTED_HIP(hipMemsetAsync(m->rank, 0, K * N * sizeof(int32_t), stream));
+    DL_HIP_CHECK(hipSetDevice(m->device));
+    DL_HIP_CHECK(hipMemcpyAsync(m->x, coords, K * N * P * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->L, loglike, K * N * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->pi, logprior, K * N * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->logx, logx, K * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->logz, logz, K * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->iter, it.data(), K * sizeof(long long), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->scale, scale, K * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->mode, modes, K * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemsetAsync(m->rank, 0, K * N * sizeof(int32_t), stream));
     // the workspaces of the context sized for the rows of a sweep before dl_nested_run (which does not allocate): one evaluation of the live points, results unused
     if (dl_eval_batch(m->ctx, m->x, (int64_t)(K * N), m->Lp, m->pip, nullptr, m->status, nullptr, stream)) return 1;
-    DL_NESTED_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     m->evaluations += (int64_t)(K * N);
     m->have_state = true;
     return 0;
@@ -459,47 +377,47 @@ int dl_nested_set_state(dl_nested* m, const double* coords, const double* loglik
 
 int dl_nested_get_state(dl_nested* m, double* coords, double* loglike, double* logprior, double* logx, double* logz, int64_t* counters, double* scale, int32_t* modes,
                         void* hip_stream) {
-    if (!m) return fail("dl_nested_get_state: null sampler");
+    if (!m) return dl_fail("dl_nested_get_state: null sampler");
     hipStream_t stream = (hipStream_t)hip_stream;
     const size_t K = m->K, N = m->N, P = m->P;
-    DL_NESTED_HIP(hipSetDevice(m->device));
-    if (coords) DL_NESTED_HIP(hipMemcpyAsync(coords, m->x, K * N * P * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (loglike) DL_NESTED_HIP(hipMemcpyAsync(loglike, m->L, K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (logprior) DL_NESTED_HIP(hipMemcpyAsync(logprior, m->pi, K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (logx) DL_NESTED_HIP(hipMemcpyAsync(logx, m->logx, K * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (logz) DL_NESTED_HIP(hipMemcpyAsync(logz, m->logz, K * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (counters) DL_NESTED_HIP(hipMemcpyAsync(counters, m->iter, K * sizeof(long long), hipMemcpyDeviceToHost, stream));
-    if (scale) DL_NESTED_HIP(hipMemcpyAsync(scale, m->scale, K * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (modes) DL_NESTED_HIP(hipMemcpyAsync(modes, m->mode, K * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    DL_NESTED_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipSetDevice(m->device));
+    if (coords) DL_HIP_CHECK(hipMemcpyAsync(coords, m->x, K * N * P * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (loglike) DL_HIP_CHECK(hipMemcpyAsync(loglike, m->L, K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (logprior) DL_HIP_CHECK(hipMemcpyAsync(logprior, m->pi, K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (logx) DL_HIP_CHECK(hipMemcpyAsync(logx, m->logx, K * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (logz) DL_HIP_CHECK(hipMemcpyAsync(logz, m->logz, K * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (counters) DL_HIP_CHECK(hipMemcpyAsync(counters, m->iter, K * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    if (scale) DL_HIP_CHECK(hipMemcpyAsync(scale, m->scale, K * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (modes) DL_HIP_CHECK(hipMemcpyAsync(modes, m->mode, K * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     return 0;
 }
 
 int dl_nested_get_decisions(dl_nested* m, int32_t* ranks, int32_t* seeds, uint8_t* accepts, double* mean, double* covariance, void* hip_stream) {
-    if (!m) return fail("dl_nested_get_decisions: null sampler");
-    if (!m->have_hyper) return fail("dl_nested_get_decisions: no hyper-parameters (dl_nested_set_hyper)");
+    if (!m) return dl_fail("dl_nested_get_decisions: null sampler");
+    if (!m->have_hyper) return dl_fail("dl_nested_get_decisions: no hyper-parameters (dl_nested_set_hyper)");
     hipStream_t stream = (hipStream_t)hip_stream;
     const size_t K = m->K, N = m->N, P = m->P, M = m->M;
-    DL_NESTED_HIP(hipSetDevice(m->device));
-    if (ranks) DL_NESTED_HIP(hipMemcpyAsync(ranks, m->rank, K * N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    if (seeds) DL_NESTED_HIP(hipMemcpyAsync(seeds, m->seeds, K * M * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    if (accepts) DL_NESTED_HIP(hipMemcpyAsync(accepts, m->flags, K * m->n_steps * M, hipMemcpyDeviceToHost, stream));
-    if (mean) DL_NESTED_HIP(hipMemcpyAsync(mean, m->mean, K * P * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (covariance) DL_NESTED_HIP(hipMemcpyAsync(covariance, m->cov, K * P * P * sizeof(double), hipMemcpyDeviceToHost, stream));
-    DL_NESTED_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipSetDevice(m->device));
+    if (ranks) DL_HIP_CHECK(hipMemcpyAsync(ranks, m->rank, K * N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (seeds) DL_HIP_CHECK(hipMemcpyAsync(seeds, m->seeds, K * M * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (accepts) DL_HIP_CHECK(hipMemcpyAsync(accepts, m->flags, K * m->n_steps * M, hipMemcpyDeviceToHost, stream));
+    if (mean) DL_HIP_CHECK(hipMemcpyAsync(mean, m->mean, K * P * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (covariance) DL_HIP_CHECK(hipMemcpyAsync(covariance, m->cov, K * P * P * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     return 0;
 }
 
 int dl_nested_run(dl_nested* m, int64_t niterations, int32_t quota, double* history_dev, double* coords_dev, double* loglike_dev, double* logprior_dev, double* logweight_dev,
                   int32_t* count_dev, int32_t* mode_dev, void* hip_stream) {
-    if (!m) return fail("dl_nested_run: null sampler");
-    if (niterations < 0 || quota < 1) return fail("dl_nested_run: invalid argument");
-    if (!history_dev || !coords_dev || !loglike_dev || !logprior_dev || !logweight_dev || !count_dev || !mode_dev) return fail("dl_nested_run: the record buffers are required");
-    if (!m->have_hyper) return fail("dl_nested_run: no hyper-parameters (dl_nested_set_hyper)");
-    if (!m->have_state) return fail("dl_nested_run: no live points (dl_nested_set_live or dl_nested_set_state)");
+    if (!m) return dl_fail("dl_nested_run: null sampler");
+    if (niterations < 0 || quota < 1) return dl_fail("dl_nested_run: invalid argument");
+    if (!history_dev || !coords_dev || !loglike_dev || !logprior_dev || !logweight_dev || !count_dev || !mode_dev) return dl_fail("dl_nested_run: the record buffers are required");
+    if (!m->have_hyper) return dl_fail("dl_nested_run: no hyper-parameters (dl_nested_set_hyper)");
+    if (!m->have_state) return dl_fail("dl_nested_run: no live points (dl_nested_set_live or dl_nested_set_state)");
     if (!niterations) return 0;
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_NESTED_HIP(hipSetDevice(m->device));
+    DL_HIP_CHECK(hipSetDevice(m->device));
     DlNestedArgs a = dl_nested_args(m);
     a.hist = history_dev; a.out_coords = coords_dev; a.out_L = loglike_dev; a.out_pi = logprior_dev; a.out_logw = logweight_dev; a.out_count = count_dev; a.out_mode = mode_dev;
     a.quota = quota;
@@ -519,7 +437,7 @@ int dl_nested_run(dl_nested* m, int64_t niterations, int32_t quota, double* hist
         hipLaunchKernelGGL(dl_nested_finish_kernel, dim3(K), dim3(DL_NESTED_THREADS), 0, stream, a);
         m->evaluations += rows * m->n_steps;
     }
-    DL_NESTED_HIP(hipGetLastError());
+    DL_HIP_CHECK(hipGetLastError());
     m->iterations += niterations;
     return 0;
 }

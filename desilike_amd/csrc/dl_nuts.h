@@ -88,8 +88,7 @@ DL_NUTS_HD double dl_nuts_logaddexp(double a, double b) {
 // standard Gaussian of component i of the momentum of trajectory `it`
 DL_NUTS_HD double dl_nuts_gauss(long long it, uint32_t chain, int i, uint32_t k0, uint32_t k1) {
     const DlPhilox r = dl_philox4x32((uint32_t)it, (uint32_t)((unsigned long long)it >> 32), chain, (uint32_t)DL_NUTS_STREAM_MOMENTUM | ((uint32_t)(i >> 1) << 8), k0, k1);
-    const double rad = sqrt(-2. * log1p(-dl_uniform53(r.x[0], r.x[1]))), ang = 6.283185307179586 * dl_uniform53(r.x[2], r.x[3]);
-    return (i & 1) ? rad * sin(ang) : rad * cos(ang);
+    return dl_box_muller(r, i);
 }
 
 // direction (+1 / -1) of doubling d and the uniform of its join

@@ -81,8 +81,7 @@ struct DlSmcArgs {
 // standard Gaussian of component i of the proposal of particle `slot`
 DL_NUTS_HD double dl_smc_gauss(long long it, int sweep, uint32_t sys, int slot, int i, uint32_t k0, uint32_t k1) {
     const DlPhilox r = dl_philox4x32((uint32_t)it, (uint32_t)sweep, sys, (uint32_t)DL_SMC_STREAM_PROPOSE | ((uint32_t)(i >> 1) << 8) | ((uint32_t)slot << 16), k0, k1);
-    const double rad = sqrt(-2. * log1p(-dl_uniform53(r.x[0], r.x[1]))), ang = 6.283185307179586 * dl_uniform53(r.x[2], r.x[3]);
-    return (i & 1) ? rad * sin(ang) : rad * cos(ang);
+    return dl_box_muller(r, i);
 }
 
 // log of the uniform of the Metropolis test of particle `slot` (-inf for the uniform 0: accepted)

@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "../../include/desilike_amd.h"
-#include "dl_kernels.h"   // dl_set_last_error
+#include "dl_sampler_dev.h"   // DlWave, DlBlock, dl_fail, DL_HIP_CHECK, dl_dev_alloc / free
 #include "dl_smc.h"
 
 #define DL_SMC_WAVES 4    // particles per workgroup of the propose and accept kernels
@@ -45,54 +45,6 @@ struct dl_smc {
 
 namespace {
 
-int fail(const std::string& msg) {
-    dl_set_last_error(msg.c_str());
-    return 1;
-}
-
-#define DL_SMC_HIP(call)                                                                              \
-    do {                                                                                              \
-        hipError_t err__ = (call);                                                                    \
-        if (err__ != hipSuccess) return fail(std::string(#call) + ": " + hipGetErrorString(err__));   \
-    } while (0)
-
-// the device's component layout: lane = component (the propose, accept, moments and Cholesky kernels)
-struct DlSmcWave {
-    static constexpr int W = 1;
-    int P, lane;
-    __device__ int comp(int) const { return lane; }
-    __device__ bool on(int) const { return lane < P; }
-    __device__ double at(const double* x, int k) const { return __shfl(x[0], k, 64); }
-    __device__ void sync() const { __syncthreads(); }      // (the Cholesky kernel's workgroup is one wavefront)
-};
-
-// the DL_SMC_THREADS threads of a system's workgroup: a wavefront's butterfly, then the wavefronts in index order
-struct DlSmcBlock {
-    int tid, n;
-    double* red;      // [2 * wavefronts] LDS
-    __device__ void sum2(double& a, double& b) const {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off, 64); b += __shfl_xor(b, off, 64); }
-        const int nw = n >> 6;
-        __syncthreads();      // (the previous reduction's reads)
-        if ((tid & 63) == 0) { red[2 * (tid >> 6)] = a; red[2 * (tid >> 6) + 1] = b; }
-        __syncthreads();
-        a = 0.; b = 0.;
-        for (int w = 0; w < nw; ++w) { a += red[2 * w]; b += red[2 * w + 1]; }
-    }
-    __device__ double max(double v) const {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-        const int nw = n >> 6;
-        __syncthreads();
-        if ((tid & 63) == 0) red[tid >> 6] = v;
-        __syncthreads();
-        v = red[0];
-        for (int w = 1; w < nw; ++w) v = fmax(v, red[w]);
-        return v;
-    }
-};
-
 __global__ __launch_bounds__(DL_SMC_THREADS) void dl_smc_temper_kernel(DlSmcArgs a) {
     __shared__ double Ls[DL_SMC_MAX_N];
     __shared__ double red[2 * DL_SMC_THREADS / 64];
@@ -107,7 +59,7 @@ __global__ __launch_bounds__(DL_SMC_THREADS) void dl_smc_temper_kernel(DlSmcArgs
         if (tid == 0) a.mode[k] = DL_SMC_REST;
         return;
     }
-    const DlSmcBlock g{tid, DL_SMC_THREADS, red};
+    const DlBlock g{tid, DL_SMC_THREADS, red};
     DlSmcLevel t;
     dl_smc_temper(g, Ls, N, beta, a.ess_fraction, &t);
     const bool temper = t.delta > 0.;
@@ -123,42 +75,15 @@ __global__ __launch_bounds__(DL_SMC_THREADS) void dl_smc_temper_kernel(DlSmcArgs
 }
 
 __global__ __launch_bounds__(64 * DL_SMC_MOMENT_WAVES) void dl_smc_moments_kernel(DlSmcArgs a) {
-    __shared__ double part[DL_SMC_MOMENT_WAVES][64];
-    const int k = blockIdx.x, row = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6, N = a.N, P = a.P;
+    const int k = blockIdx.x, row = blockIdx.y, N = a.N, P = a.P;
     if (a.mode[k] != DL_SMC_TEMPER) return;      // (the whole workgroup)
-    const DlSmcWave l{P, lane};
-    const double *x = a.x[a.cur] + (size_t)k * N * P, *W = a.W + (size_t)k * N;
-    DlNutsVec<DlSmcWave> m, acc;
-    m.x[0] = 0.;
-    dl_smc_moment_partial(l, x, W, N, w, DL_SMC_MOMENT_WAVES, -1, m, 0., acc);
-    part[w][lane] = acc.x[0];
-    __syncthreads();
-    double s = 0.;
-    for (int v = 0; v < DL_SMC_MOMENT_WAVES; ++v) s += part[v][lane];
-    m.x[0] = s;
-    const double mrow = __shfl(s, row, 64);
-    __syncthreads();
-    dl_smc_moment_partial(l, x, W, N, w, DL_SMC_MOMENT_WAVES, row, m, mrow, acc);
-    part[w][lane] = acc.x[0];
-    __syncthreads();
-    if (w == 0 && lane < P) {
-        s = 0.;
-        for (int v = 0; v < DL_SMC_MOMENT_WAVES; ++v) s += part[v][lane];
-        if (lane <= row) a.cov[((size_t)k * P + row) * P + lane] = s;
-        if (row == 0) a.mean[(size_t)k * P + lane] = x[lane] + m.x[0];
-    }
+    dl_pop_moments_row(a, a.x[a.cur] + (size_t)k * N * P, a.W + (size_t)k * N, N, k, row);
 }
 
 __global__ __launch_bounds__(64) void dl_smc_cholesky_kernel(DlSmcArgs a) {
-    __shared__ double C[DL_SMC_MAX_P * DL_SMC_MAX_P];
-    const int k = blockIdx.x, lane = threadIdx.x, P = a.P;
+    const int k = blockIdx.x, P = a.P;
     if (a.mode[k] != DL_SMC_TEMPER) return;
-    const DlSmcWave l{P, lane};
-    for (int e = lane; e < P * P; e += 64) C[e] = 0.;
-    __syncthreads();
-    dl_smc_factor(l, a.cov + (size_t)k * P * P, a.widths, C);
-    double* out = a.chol + (size_t)k * P * P;
-    for (int e = lane; e < P * P; e += 64) out[e] = C[e];
+    dl_pop_cholesky(P, a.cov + (size_t)k * P * P, a.widths, a.chol + (size_t)k * P * P);
 }
 
 __global__ __launch_bounds__(DL_SMC_THREADS) void dl_smc_resample_kernel(DlSmcArgs a) {
@@ -201,8 +126,8 @@ __global__ __launch_bounds__(64 * DL_SMC_WAVES) void dl_smc_propose_kernel(DlSmc
     const long long r = (long long)blockIdx.x * DL_SMC_WAVES + (threadIdx.x >> 6);
     if (r >= (long long)a.K * N) return;     // (whole wavefronts)
     const int k = (int)(r / N), i = (int)(r - (long long)k * N);
-    const DlSmcWave l{P, lane};
-    DlNutsVec<DlSmcWave> x, xp;
+    const DlWave l{P, lane};
+    DlNutsVec<DlWave> x, xp;
     dl_nuts_load(l, x, a.x[a.cur] + (size_t)r * P);
     if (a.mode[k] == DL_SMC_REST) {          // its row is evaluated and ignored
         dl_nuts_store(l, x, a.prop + (size_t)r * P);
@@ -221,12 +146,12 @@ __global__ __launch_bounds__(64 * DL_SMC_WAVES) void dl_smc_accept_kernel(DlSmcA
     if (r >= (long long)K * N) return;
     const int k = (int)(r / N), i = (int)(r - (long long)k * N);
     if (a.mode[k] == DL_SMC_REST) return;
-    const DlSmcWave l{P, lane};
+    const DlWave l{P, lane};
     double *L = a.L[a.cur] + r, *pi = a.pi[a.cur] + r, *x = a.x[a.cur] + (size_t)r * P;
     const double logu = dl_smc_log_uniform(a.iter[k], sweep, (uint32_t)a.sys_ids[k], i, a.k0, a.k1);
     double Lc = *L, pic = *pi;
     const bool accept = dl_smc_accept(a.beta[k], Lc, pic, a.Lp[r], a.pip[r], a.status[r], logu);
-    DlNutsVec<DlSmcWave> v;
+    DlNutsVec<DlWave> v;
     if (accept) {
         dl_nuts_load(l, v, a.prop + (size_t)r * P);
         dl_nuts_store(l, v, x);
@@ -273,16 +198,6 @@ DlSmcArgs dl_smc_args(const dl_smc* m) {
     return a;
 }
 
-template <class T>
-bool dl_smc_alloc(T** p, size_t n) {
-    return hipMalloc((void**)p, n * sizeof(T)) == hipSuccess && hipMemset(*p, 0, n * sizeof(T)) == hipSuccess;
-}
-
-void dl_smc_free_sweeps(dl_smc* m) {
-    for (void** p : {(void**)&m->sscale, (void**)&m->acc, (void**)&m->flags})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-}
-
 }  // namespace
 
 extern "C" {
@@ -290,7 +205,7 @@ extern "C" {
 void dl_smc_destroy(dl_smc* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    dl_smc_free_sweeps(m);
+    dl_dev_free({(void**)&m->sscale, (void**)&m->acc, (void**)&m->flags});
     for (void* p : {(void*)m->x[0], (void*)m->x[1], (void*)m->L[0], (void*)m->L[1], (void*)m->pi[0], (void*)m->pi[1], (void*)m->beta, (void*)m->logz, (void*)m->scale,
                     (void*)m->W, (void*)m->cum, (void*)m->mean, (void*)m->cov, (void*)m->chol, (void*)m->widths, (void*)m->tmp, (void*)m->prop, (void*)m->Lp, (void*)m->pip,
                     (void*)m->sys_ids, (void*)m->anc, (void*)m->mode, (void*)m->status, (void*)m->iter})
@@ -299,31 +214,31 @@ void dl_smc_destroy(dl_smc* m) {
 }
 
 int dl_smc_create(dl_smc** out, dl_ctx* ctx, int32_t nsystems, int32_t nparticles, const int32_t* system_ids, uint64_t seed, double offset, const double* widths) {
-    if (!out || !ctx || !widths) return fail("dl_smc_create: null argument");
+    if (!out || !ctx || !widths) return dl_fail("dl_smc_create: null argument");
     *out = nullptr;
     const int P = (int)dl_info(ctx, "n_params");
-    if (P < 1 || P > DL_SMC_MAX_P) return fail("dl_smc_create: the sampler takes 1 .. 64 parameters, the context has " + std::to_string(P));
-    if (nsystems < 1) return fail("dl_smc_create: nsystems must be >= 1");
-    if (nparticles < 64 || nparticles > DL_SMC_MAX_N || nparticles % 64) return fail("dl_smc_create: nparticles must be a multiple of 64 between 64 and 16384");
-    if (!std::isfinite(offset)) return fail("dl_smc_create: the offset must be finite");
+    if (P < 1 || P > DL_SMC_MAX_P) return dl_fail("dl_smc_create: the sampler takes 1 .. 64 parameters, the context has " + std::to_string(P));
+    if (nsystems < 1) return dl_fail("dl_smc_create: nsystems must be >= 1");
+    if (nparticles < 64 || nparticles > DL_SMC_MAX_N || nparticles % 64) return dl_fail("dl_smc_create: nparticles must be a multiple of 64 between 64 and 16384");
+    if (!std::isfinite(offset)) return dl_fail("dl_smc_create: the offset must be finite");
     std::vector<int32_t> ids(nsystems);
     for (int k = 0; k < nsystems; ++k) {
         ids[k] = system_ids ? system_ids[k] : k;
-        if (ids[k] < 0) return fail("dl_smc_create: system ids must be non-negative");
+        if (ids[k] < 0) return dl_fail("dl_smc_create: system ids must be non-negative");
     }
     for (int i = 0; i < P; ++i)
-        if (!(widths[i] > 0.) || !std::isfinite(widths[i])) return fail("dl_smc_create: the priors' widths must be positive and finite");
+        if (!(widths[i] > 0.) || !std::isfinite(widths[i])) return dl_fail("dl_smc_create: the priors' widths must be positive and finite");
     dl_smc* m = new dl_smc();
     m->ctx = ctx; m->device = (int)dl_info(ctx, "device"); m->K = nsystems; m->N = nparticles; m->P = P; m->seed = seed; m->offset = offset; m->ids = ids;
-    auto bail = [&](const std::string& msg) { dl_smc_destroy(m); return fail(msg); };
+    auto bail = [&](const std::string& msg) { dl_smc_destroy(m); return dl_fail(msg); };
     if (hipSetDevice(m->device) != hipSuccess) return bail("dl_smc_create: hipSetDevice failed");
     const size_t K = nsystems, N = nparticles, p = P;
     bool ok = true;
-    for (int b = 0; b < 2; ++b) ok = ok && dl_smc_alloc(&m->x[b], K * N * p) && dl_smc_alloc(&m->L[b], K * N) && dl_smc_alloc(&m->pi[b], K * N);
-    ok = ok && dl_smc_alloc(&m->beta, K) && dl_smc_alloc(&m->logz, K) && dl_smc_alloc(&m->scale, K) && dl_smc_alloc(&m->W, K * N) && dl_smc_alloc(&m->cum, K * N) &&
-         dl_smc_alloc(&m->mean, K * p) && dl_smc_alloc(&m->cov, K * p * p) && dl_smc_alloc(&m->chol, K * p * p) && dl_smc_alloc(&m->widths, p) &&
-         dl_smc_alloc(&m->tmp, (size_t)DL_SMC_NT * K) && dl_smc_alloc(&m->prop, K * N * p) && dl_smc_alloc(&m->Lp, K * N) && dl_smc_alloc(&m->pip, K * N) &&
-         dl_smc_alloc(&m->sys_ids, K) && dl_smc_alloc(&m->anc, K * N) && dl_smc_alloc(&m->mode, K) && dl_smc_alloc(&m->status, K * N) && dl_smc_alloc(&m->iter, K);
+    for (int b = 0; b < 2; ++b) ok = ok && dl_dev_alloc(&m->x[b], K * N * p) && dl_dev_alloc(&m->L[b], K * N) && dl_dev_alloc(&m->pi[b], K * N);
+    ok = ok && dl_dev_alloc(&m->beta, K) && dl_dev_alloc(&m->logz, K) && dl_dev_alloc(&m->scale, K) && dl_dev_alloc(&m->W, K * N) && dl_dev_alloc(&m->cum, K * N) &&
+         dl_dev_alloc(&m->mean, K * p) && dl_dev_alloc(&m->cov, K * p * p) && dl_dev_alloc(&m->chol, K * p * p) && dl_dev_alloc(&m->widths, p) &&
+         dl_dev_alloc(&m->tmp, (size_t)DL_SMC_NT * K) && dl_dev_alloc(&m->prop, K * N * p) && dl_dev_alloc(&m->Lp, K * N) && dl_dev_alloc(&m->pip, K * N) &&
+         dl_dev_alloc(&m->sys_ids, K) && dl_dev_alloc(&m->anc, K * N) && dl_dev_alloc(&m->mode, K) && dl_dev_alloc(&m->status, K * N) && dl_dev_alloc(&m->iter, K);
     if (!ok) return bail("dl_smc_create: device allocation failed");
     ok = hipMemcpy(m->sys_ids, ids.data(), K * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(m->widths, widths, p * sizeof(double), hipMemcpyHostToDevice) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
@@ -333,65 +248,65 @@ int dl_smc_create(dl_smc** out, dl_ctx* ctx, int32_t nsystems, int32_t nparticle
 }
 
 int dl_smc_set_hyper(dl_smc* m, double ess_fraction, int32_t n_steps, double target_acceptance, double scale, void* hip_stream) {
-    if (!m) return fail("dl_smc_set_hyper: null sampler");
-    if (!(ess_fraction > 0.) || !(ess_fraction < 1.)) return fail("dl_smc_set_hyper: ess_fraction must lie in (0, 1)");
-    if (n_steps < 1 || n_steps > DL_SMC_MAX_STEPS) return fail("dl_smc_set_hyper: n_steps must lie in 1 .. 1024");
-    if (!(target_acceptance > 0.) || !(target_acceptance < 1.)) return fail("dl_smc_set_hyper: target_acceptance must lie in (0, 1)");
-    if (!(scale >= 1e-3) || !(scale <= 1e3)) return fail("dl_smc_set_hyper: scale must lie in 1e-3 .. 1e3");
+    if (!m) return dl_fail("dl_smc_set_hyper: null sampler");
+    if (!(ess_fraction > 0.) || !(ess_fraction < 1.)) return dl_fail("dl_smc_set_hyper: ess_fraction must lie in (0, 1)");
+    if (n_steps < 1 || n_steps > DL_SMC_MAX_STEPS) return dl_fail("dl_smc_set_hyper: n_steps must lie in 1 .. 1024");
+    if (!(target_acceptance > 0.) || !(target_acceptance < 1.)) return dl_fail("dl_smc_set_hyper: target_acceptance must lie in (0, 1)");
+    if (!(scale >= 1e-3) || !(scale <= 1e3)) return dl_fail("dl_smc_set_hyper: scale must lie in 1e-3 .. 1e3");
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_SMC_HIP(hipSetDevice(m->device));
+    DL_HIP_CHECK(hipSetDevice(m->device));
     const size_t K = m->K, N = m->N;
     if (n_steps != m->n_steps) {
-        DL_SMC_HIP(hipDeviceSynchronize());      // kernels of earlier calls may still use the buffers about to be freed
-        dl_smc_free_sweeps(m);
+        DL_HIP_CHECK(hipDeviceSynchronize());      // kernels of earlier calls may still use the buffers about to be freed
+        dl_dev_free({(void**)&m->sscale, (void**)&m->acc, (void**)&m->flags});
         m->n_steps = 0;
-        if (!(dl_smc_alloc(&m->sscale, K * n_steps) && dl_smc_alloc(&m->acc, K * n_steps) && dl_smc_alloc(&m->flags, K * n_steps * N)))
-            return fail("dl_smc_set_hyper: device allocation failed");
-        DL_SMC_HIP(hipDeviceSynchronize());
+        if (!(dl_dev_alloc(&m->sscale, K * n_steps) && dl_dev_alloc(&m->acc, K * n_steps) && dl_dev_alloc(&m->flags, K * n_steps * N)))
+            return dl_fail("dl_smc_set_hyper: device allocation failed");
+        DL_HIP_CHECK(hipDeviceSynchronize());
         m->n_steps = n_steps;
     }
     std::vector<double> s(K, scale);
-    DL_SMC_HIP(hipMemcpyAsync(m->scale, s.data(), K * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_SMC_HIP(hipStreamSynchronize(stream));   // the host buffer is pageable
+    DL_HIP_CHECK(hipMemcpyAsync(m->scale, s.data(), K * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));   // the host buffer is pageable
     m->ess_fraction = ess_fraction; m->target_acceptance = target_acceptance;
     m->have_hyper = true;
     return 0;
 }
 
 int dl_smc_set_particles(dl_smc* m, const double* coords, void* hip_stream) {
-    if (!m || !coords) return fail("dl_smc_set_particles: null argument");
+    if (!m || !coords) return dl_fail("dl_smc_set_particles: null argument");
     hipStream_t stream = (hipStream_t)hip_stream;
     const size_t K = m->K, N = m->N, P = m->P;
     for (size_t e = 0; e < K * N * P; ++e)
-        if (!std::isfinite(coords[e])) return fail("dl_smc_set_particles: the particles must be finite");
+        if (!std::isfinite(coords[e])) return dl_fail("dl_smc_set_particles: the particles must be finite");
     m->have_state = false;
-    DL_SMC_HIP(hipSetDevice(m->device));
-    DL_SMC_HIP(hipMemcpyAsync(m->x[0], coords, K * N * P * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipSetDevice(m->device));
+    DL_HIP_CHECK(hipMemcpyAsync(m->x[0], coords, K * N * P * sizeof(double), hipMemcpyHostToDevice, stream));
     if (dl_eval_batch(m->ctx, m->x[0], (int64_t)(K * N), m->L[0], m->pi[0], nullptr, m->status, nullptr, stream)) return 1;
     std::vector<double> L(K * N), pi(K * N);
     std::vector<int32_t> status(K * N);
-    DL_SMC_HIP(hipMemcpyAsync(L.data(), m->L[0], K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
-    DL_SMC_HIP(hipMemcpyAsync(pi.data(), m->pi[0], K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
-    DL_SMC_HIP(hipMemcpyAsync(status.data(), m->status, K * N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    DL_SMC_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipMemcpyAsync(L.data(), m->L[0], K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(pi.data(), m->pi[0], K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(status.data(), m->status, K * N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     m->evaluations += (int64_t)(K * N);
     for (size_t k = 0; k < K; ++k) {
         size_t live = 0;
         for (size_t i = 0; i < N; ++i) {
             const size_t r = k * N + i;
             if (!std::isfinite(pi[r]))
-                return fail("dl_smc_set_particles: particle " + std::to_string(i) + " of system " + std::to_string(k) + " lies outside the prior (its log-prior is not finite)");
+                return dl_fail("dl_smc_set_particles: particle " + std::to_string(i) + " of system " + std::to_string(k) + " lies outside the prior (its log-prior is not finite)");
             if (status[r] != 0 || !std::isfinite(L[r])) L[r] = -HUGE_VAL;      // a dead particle: weight 0 at every temperature
             else ++live;
         }
-        if (!live) return fail("dl_smc_set_particles: no particle of system " + std::to_string(k) + " has a finite log-likelihood");
+        if (!live) return dl_fail("dl_smc_set_particles: no particle of system " + std::to_string(k) + " has a finite log-likelihood");
     }
-    DL_SMC_HIP(hipMemcpyAsync(m->L[0], L.data(), K * N * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_SMC_HIP(hipMemsetAsync(m->beta, 0, K * sizeof(double), stream));
-    DL_SMC_HIP(hipMemsetAsync(m->logz, 0, K * sizeof(double), stream));
-    DL_SMC_HIP(hipMemsetAsync(m->iter, 0, K * sizeof(long long), stream));
-    DL_SMC_HIP(hipMemsetAsync(m->chol, 0, K * P * P * sizeof(double), stream));
-    DL_SMC_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->L[0], L.data(), K * N * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemsetAsync(m->beta, 0, K * sizeof(double), stream));
+    DL_HIP_CHECK(hipMemsetAsync(m->logz, 0, K * sizeof(double), stream));
+    DL_HIP_CHECK(hipMemsetAsync(m->iter, 0, K * sizeof(long long), stream));
+    DL_HIP_CHECK(hipMemsetAsync(m->chol, 0, K * P * P * sizeof(double), stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     m->cur = 0; m->iterations = 0;
     m->have_state = true;
     return 0;
@@ -399,35 +314,35 @@ int dl_smc_set_particles(dl_smc* m, const double* coords, void* hip_stream) {
 
 int dl_smc_set_state(dl_smc* m, const double* coords, const double* loglike, const double* logprior, const double* beta, const double* logz, const int64_t* counters,
                      const double* scale, const double* factor, void* hip_stream) {
-    if (!m || !coords || !loglike || !logprior || !beta || !logz || !counters || !scale || !factor) return fail("dl_smc_set_state: null argument");
+    if (!m || !coords || !loglike || !logprior || !beta || !logz || !counters || !scale || !factor) return dl_fail("dl_smc_set_state: null argument");
     hipStream_t stream = (hipStream_t)hip_stream;
     const size_t K = m->K, N = m->N, P = m->P;
     std::vector<long long> it(K);
     for (size_t k = 0; k < K; ++k) {
-        if (!(beta[k] >= 0.) || !(beta[k] <= 1.)) return fail("dl_smc_set_state: beta must lie in 0 .. 1");
-        if (counters[k] < 0) return fail("dl_smc_set_state: negative iteration counter");
-        if (!(scale[k] >= 1e-3) || !(scale[k] <= 1e3)) return fail("dl_smc_set_state: scale must lie in 1e-3 .. 1e3");
-        if (!std::isfinite(logz[k])) return fail("dl_smc_set_state: logz must be finite");
+        if (!(beta[k] >= 0.) || !(beta[k] <= 1.)) return dl_fail("dl_smc_set_state: beta must lie in 0 .. 1");
+        if (counters[k] < 0) return dl_fail("dl_smc_set_state: negative iteration counter");
+        if (!(scale[k] >= 1e-3) || !(scale[k] <= 1e3)) return dl_fail("dl_smc_set_state: scale must lie in 1e-3 .. 1e3");
+        if (!std::isfinite(logz[k])) return dl_fail("dl_smc_set_state: logz must be finite");
         it[k] = counters[k];
     }
     for (size_t e = 0; e < K * N * P; ++e)
-        if (!std::isfinite(coords[e])) return fail("dl_smc_set_state: the particles must be finite");
+        if (!std::isfinite(coords[e])) return dl_fail("dl_smc_set_state: the particles must be finite");
     for (size_t e = 0; e < K * N; ++e)
-        if (!std::isfinite(logprior[e]) || std::isnan(loglike[e]) || loglike[e] == HUGE_VAL) return fail("dl_smc_set_state: log-priors must be finite, log-likelihoods finite or -inf");
+        if (!std::isfinite(logprior[e]) || std::isnan(loglike[e]) || loglike[e] == HUGE_VAL) return dl_fail("dl_smc_set_state: log-priors must be finite, log-likelihoods finite or -inf");
     for (size_t e = 0; e < K * P * P; ++e)
-        if (!std::isfinite(factor[e])) return fail("dl_smc_set_state: the factor must be finite");
-    DL_SMC_HIP(hipSetDevice(m->device));
-    DL_SMC_HIP(hipMemcpyAsync(m->x[0], coords, K * N * P * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_SMC_HIP(hipMemcpyAsync(m->L[0], loglike, K * N * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_SMC_HIP(hipMemcpyAsync(m->pi[0], logprior, K * N * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_SMC_HIP(hipMemcpyAsync(m->beta, beta, K * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_SMC_HIP(hipMemcpyAsync(m->logz, logz, K * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_SMC_HIP(hipMemcpyAsync(m->iter, it.data(), K * sizeof(long long), hipMemcpyHostToDevice, stream));
-    DL_SMC_HIP(hipMemcpyAsync(m->scale, scale, K * sizeof(double), hipMemcpyHostToDevice, stream));
-    DL_SMC_HIP(hipMemcpyAsync(m->chol, factor, K * P * P * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (!std::isfinite(factor[e])) return dl_fail("dl_smc_set_state: the factor must be finite");
+    DL_HIP_CHECK(hipSetDevice(m->device));
+    DL_HIP_CHECK(hipMemcpyAsync(m->x[0], coords, K * N * P * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->L[0], loglike, K * N * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->pi[0], logprior, K * N * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->beta, beta, K * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->logz, logz, K * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->iter, it.data(), K * sizeof(long long), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->scale, scale, K * sizeof(double), hipMemcpyHostToDevice, stream));
+    DL_HIP_CHECK(hipMemcpyAsync(m->chol, factor, K * P * P * sizeof(double), hipMemcpyHostToDevice, stream));
     // the workspaces of the context sized for the K N rows of a sweep before dl_smc_run (which does not allocate): one evaluation of the particles, results unused
     if (dl_eval_batch(m->ctx, m->x[0], (int64_t)(K * N), m->Lp, m->pip, nullptr, m->status, nullptr, stream)) return 1;
-    DL_SMC_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     m->evaluations += (int64_t)(K * N);
     m->cur = 0;
     m->have_state = true;
@@ -436,46 +351,46 @@ int dl_smc_set_state(dl_smc* m, const double* coords, const double* loglike, con
 
 int dl_smc_get_state(dl_smc* m, double* coords, double* loglike, double* logprior, double* beta, double* logz, int64_t* counters, double* scale, double* factor,
                      void* hip_stream) {
-    if (!m) return fail("dl_smc_get_state: null sampler");
+    if (!m) return dl_fail("dl_smc_get_state: null sampler");
     hipStream_t stream = (hipStream_t)hip_stream;
     const size_t K = m->K, N = m->N, P = m->P;
     const int c = m->cur;
-    DL_SMC_HIP(hipSetDevice(m->device));
-    if (coords) DL_SMC_HIP(hipMemcpyAsync(coords, m->x[c], K * N * P * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (loglike) DL_SMC_HIP(hipMemcpyAsync(loglike, m->L[c], K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (logprior) DL_SMC_HIP(hipMemcpyAsync(logprior, m->pi[c], K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (beta) DL_SMC_HIP(hipMemcpyAsync(beta, m->beta, K * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (logz) DL_SMC_HIP(hipMemcpyAsync(logz, m->logz, K * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (counters) DL_SMC_HIP(hipMemcpyAsync(counters, m->iter, K * sizeof(long long), hipMemcpyDeviceToHost, stream));
-    if (scale) DL_SMC_HIP(hipMemcpyAsync(scale, m->scale, K * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (factor) DL_SMC_HIP(hipMemcpyAsync(factor, m->chol, K * P * P * sizeof(double), hipMemcpyDeviceToHost, stream));
-    DL_SMC_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipSetDevice(m->device));
+    if (coords) DL_HIP_CHECK(hipMemcpyAsync(coords, m->x[c], K * N * P * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (loglike) DL_HIP_CHECK(hipMemcpyAsync(loglike, m->L[c], K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (logprior) DL_HIP_CHECK(hipMemcpyAsync(logprior, m->pi[c], K * N * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (beta) DL_HIP_CHECK(hipMemcpyAsync(beta, m->beta, K * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (logz) DL_HIP_CHECK(hipMemcpyAsync(logz, m->logz, K * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (counters) DL_HIP_CHECK(hipMemcpyAsync(counters, m->iter, K * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    if (scale) DL_HIP_CHECK(hipMemcpyAsync(scale, m->scale, K * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (factor) DL_HIP_CHECK(hipMemcpyAsync(factor, m->chol, K * P * P * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     return 0;
 }
 
 int dl_smc_get_decisions(dl_smc* m, int32_t* ancestors, uint8_t* accepts, double* mean, double* covariance, void* hip_stream) {
-    if (!m) return fail("dl_smc_get_decisions: null sampler");
-    if (!m->n_steps) return fail("dl_smc_get_decisions: no hyper-parameters (dl_smc_set_hyper)");
+    if (!m) return dl_fail("dl_smc_get_decisions: null sampler");
+    if (!m->n_steps) return dl_fail("dl_smc_get_decisions: no hyper-parameters (dl_smc_set_hyper)");
     hipStream_t stream = (hipStream_t)hip_stream;
     const size_t K = m->K, N = m->N, P = m->P;
-    DL_SMC_HIP(hipSetDevice(m->device));
-    if (ancestors) DL_SMC_HIP(hipMemcpyAsync(ancestors, m->anc, K * N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    if (accepts) DL_SMC_HIP(hipMemcpyAsync(accepts, m->flags, K * m->n_steps * N, hipMemcpyDeviceToHost, stream));
-    if (mean) DL_SMC_HIP(hipMemcpyAsync(mean, m->mean, K * P * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (covariance) DL_SMC_HIP(hipMemcpyAsync(covariance, m->cov, K * P * P * sizeof(double), hipMemcpyDeviceToHost, stream));
-    DL_SMC_HIP(hipStreamSynchronize(stream));
+    DL_HIP_CHECK(hipSetDevice(m->device));
+    if (ancestors) DL_HIP_CHECK(hipMemcpyAsync(ancestors, m->anc, K * N * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (accepts) DL_HIP_CHECK(hipMemcpyAsync(accepts, m->flags, K * m->n_steps * N, hipMemcpyDeviceToHost, stream));
+    if (mean) DL_HIP_CHECK(hipMemcpyAsync(mean, m->mean, K * P * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (covariance) DL_HIP_CHECK(hipMemcpyAsync(covariance, m->cov, K * P * P * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DL_HIP_CHECK(hipStreamSynchronize(stream));
     return 0;
 }
 
 int dl_smc_run(dl_smc* m, int64_t niterations, int32_t quota, double* history_dev, double* coords_dev, double* logp_dev, int32_t* count_dev, void* hip_stream) {
-    if (!m) return fail("dl_smc_run: null sampler");
-    if (niterations < 0 || quota < 1) return fail("dl_smc_run: invalid argument");
-    if (!history_dev || !coords_dev || !logp_dev || !count_dev) return fail("dl_smc_run: the record buffers are required");
-    if (!m->have_hyper) return fail("dl_smc_run: no hyper-parameters (dl_smc_set_hyper)");
-    if (!m->have_state) return fail("dl_smc_run: no particles (dl_smc_set_particles or dl_smc_set_state)");
+    if (!m) return dl_fail("dl_smc_run: null sampler");
+    if (niterations < 0 || quota < 1) return dl_fail("dl_smc_run: invalid argument");
+    if (!history_dev || !coords_dev || !logp_dev || !count_dev) return dl_fail("dl_smc_run: the record buffers are required");
+    if (!m->have_hyper) return dl_fail("dl_smc_run: no hyper-parameters (dl_smc_set_hyper)");
+    if (!m->have_state) return dl_fail("dl_smc_run: no particles (dl_smc_set_particles or dl_smc_set_state)");
     if (!niterations) return 0;
     hipStream_t stream = (hipStream_t)hip_stream;
-    DL_SMC_HIP(hipSetDevice(m->device));
+    DL_HIP_CHECK(hipSetDevice(m->device));
     DlSmcArgs a = dl_smc_args(m);
     a.hist = history_dev; a.out_coords = coords_dev; a.out_logp = logp_dev; a.out_count = count_dev; a.quota = quota;
     const int K = m->K, P = m->P;
@@ -497,7 +412,7 @@ int dl_smc_run(dl_smc* m, int64_t niterations, int32_t quota, double* history_de
         hipLaunchKernelGGL(dl_smc_finish_kernel, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, stream, a);
         m->evaluations += rows * m->n_steps;
     }
-    DL_SMC_HIP(hipGetLastError());
+    DL_HIP_CHECK(hipGetLastError());
     m->iterations += niterations;
     return 0;
 }

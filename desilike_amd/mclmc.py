@@ -30,10 +30,7 @@ class _MclmcDraws(_Draws):
         it, chain = np.asarray(it, dtype='i8'), np.asarray(chain)
         z = np.empty((len(it), P + (P & 1)))
         for j in range((P + 1) // 2):
-            w = self._words(it, chain, np.full(len(it), stream | (j << 8), dtype=np.uint32))
-            rad = np.sqrt(-2. * np.log1p(-CounterRNG.uniform53(w[:, 0], w[:, 1])))
-            ang = 6.283185307179586 * CounterRNG.uniform53(w[:, 2], w[:, 3])
-            z[:, 2 * j], z[:, 2 * j + 1] = rad * np.cos(ang), rad * np.sin(ang)
+            z[:, 2 * j], z[:, 2 * j + 1] = CounterRNG.box_muller(self._words(it, chain, np.full(len(it), stream | (j << 8), dtype=np.uint32)))
         return z[:, :P]
 
 

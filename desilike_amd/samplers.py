@@ -51,6 +51,13 @@ class CounterRNG(object):
         """53-bit uniform on [0, 1) from two 32-bit words (numpy's ``random_sample`` construction)."""
         return ((hi >> np.uint32(5)).astype('f8') * 67108864. + (lo >> np.uint32(6)).astype('f8')) / 9007199254740992.
 
+    @staticmethod
+    def box_muller(words):
+        """The two standard Gaussians of the blocks ``words [..., 4]`` (dl_box_muller of csrc/dl_philox.h): radius from words 0, 1, angle from words 2, 3."""
+        rad = np.sqrt(-2. * np.log1p(-CounterRNG.uniform53(words[..., 0], words[..., 1])))
+        ang = 6.283185307179586 * CounterRNG.uniform53(words[..., 2], words[..., 3])
+        return rad * np.cos(ang), rad * np.sin(ang)
+
     def permutation(self, iteration, n):
         """Random split of the ensemble: position r of the permutation holds walker F(r), F a keyed bijection of [0, n) -- four rounds of (odd multiplier, offset)
         mod 2^m followed by a right xor-shift, m = bit length of n - 1, keys = eight Philox words of the iteration, cycle-walked back into [0, n).  Every element

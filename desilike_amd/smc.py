@@ -34,10 +34,7 @@ class _SmcDraws(_Draws):
         slots = np.arange(N, dtype=np.uint32) << np.uint32(16)
         z = np.empty((N, P + (P & 1)))
         for j in range((P + 1) // 2):
-            w = self._slots(it, sweep, system, np.uint32(STREAM_PROPOSE | (j << 8)) | slots)
-            rad = np.sqrt(-2. * np.log1p(-CounterRNG.uniform53(w[:, 0], w[:, 1])))
-            ang = 6.283185307179586 * CounterRNG.uniform53(w[:, 2], w[:, 3])
-            z[:, 2 * j], z[:, 2 * j + 1] = rad * np.cos(ang), rad * np.sin(ang)
+            z[:, 2 * j], z[:, 2 * j + 1] = CounterRNG.box_muller(self._slots(it, sweep, system, np.uint32(STREAM_PROPOSE | (j << 8)) | slots))
         return z[:, :P]
 
     def log_uniform(self, it, sweep, system, N):

@@ -26,10 +26,7 @@ def gauss(seed, index, draw, ns):
         counter = np.empty(shape + (4,), dtype=np.uint32)
         counter[..., 0], counter[..., 1] = (index & np.uint64(0xFFFFFFFF)).astype(np.uint32), (index >> np.uint64(32)).astype(np.uint32)
         counter[..., 2], counter[..., 3] = draw, SOLVED_STREAM | (pair << 8)
-        w = CounterRNG.philox4x32(counter, key)
-        rad = np.sqrt(-2. * np.log1p(-CounterRNG.uniform53(w[..., 0], w[..., 1])))
-        ang = 6.283185307179586 * CounterRNG.uniform53(w[..., 2], w[..., 3])
-        z[..., 2 * pair], z[..., 2 * pair + 1] = rad * np.cos(ang), rad * np.sin(ang)
+        z[..., 2 * pair], z[..., 2 * pair + 1] = CounterRNG.box_muller(CounterRNG.philox4x32(counter, key))
     return z[..., :ns]
 
 

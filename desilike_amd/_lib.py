@@ -184,6 +184,90 @@ def _i32_ptr(array):
     return None if array is None else array.ctypes.data_as(_c_int32_p)
 
 
+_POINTERS = {'f8': _c_double_p, 'i8': ctypes.POINTER(ctypes.c_int64), 'i4': _c_int32_p}
+
+
+def _ptr(array):
+    """Pointer of the array's own type (float64 / int64 / int32; ``None`` stays ``None``): a state array travels with the dtype its table gives it."""
+    return None if array is None else array.ctypes.data_as(_POINTERS[array.dtype.str[1:]])
+
+
+def _seed(seed):
+    return ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _refuse_expand(ctx, does='sampler moves'):
+    """The device-resident samplers work in the columns of the device context, which do not hold the parameters derived by an expression."""
+    if ctx.expand is not None:
+        raise NotImplementedError('the device-resident {} in the columns of the device context: parameters derived by an expression need the host-driven sampler'.format(does))
+
+
+def _ids(ids, n, unit):
+    """``<unit>_ids`` (default 0 .. n - 1) as contiguous int32 [n]."""
+    ids = np.ascontiguousarray(np.arange(n) if ids is None else ids, dtype='i4')
+    if len(ids) != n: raise ValueError('{0}_ids must have one entry per {0}'.format(unit))
+    return ids
+
+
+def _fd_table(table, n_params):
+    """Steps or prior bounds [P, 2] of the central differences (``None``: the library's default)."""
+    return None if table is None else np.ascontiguousarray(table, dtype='f8').reshape(n_params, 2)
+
+
+def _state_in(values, table):
+    """The arrays of a ``set_state`` in the dtypes and shapes of the owner's state ``table`` [(dtype, shape), ...]."""
+    return [np.ascontiguousarray(value, dtype=dtype).reshape(shape) for value, (dtype, shape) in zip(values, table)]
+
+
+def _state_out(table):
+    return [np.empty(shape, dtype=dtype) for dtype, shape in table]
+
+
+def _record_buffers(device, table):
+    """One tensor on ``cuda:device`` per (dtype, shape, fill) of ``table``; fill ``None``: not initialised."""
+    import torch
+    device, dtypes = torch.device('cuda', device), {'f8': torch.float64, 'i8': torch.int64, 'i4': torch.int32}
+    return tuple(torch.empty(shape, dtype=dtypes[dtype], device=device) if fill is None else torch.full(shape, fill, dtype=dtypes[dtype], device=device)
+                 for dtype, shape, fill in table)
+
+
+class _Handle(object):
+    """Owner of one C handle of the family ``<_prefix>_*`` (include/desilike_amd.h): made by ``<_prefix>_create``, destroyed once by ``<_prefix>_destroy``.  ``device``
+    (set by the subclass) is the GPU whose current stream is the default of every call."""
+    _prefix = None
+
+    def _create(self, *args):
+        """``<_prefix>_create(&handle, *args)``; until it has succeeded there is no ``_handle``, and :meth:`close` / ``__del__`` of a half-built owner do nothing."""
+        self._lib = load()
+        handle = ctypes.c_void_p()
+        if getattr(self._lib, self._prefix + '_create')(ctypes.byref(handle), *args) != 0:
+            raise LibraryError(self._lib.dl_last_error(None).decode())
+        self._handle = handle
+
+    def _check(self, rc):
+        if rc != 0:
+            raise LibraryError(self._lib.dl_last_error(None).decode())
+
+    def _stream(self, stream):
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream(torch.device('cuda', self.device)).cuda_stream if stream is None else stream)
+
+    def info(self, key):
+        """``<_prefix>_info`` (the families that export it)."""
+        return int(getattr(self._lib, self._prefix + '_info')(self._handle, key.encode()))
+
+    def close(self):
+        if getattr(self, '_handle', None):
+            getattr(self._lib, self._prefix + '_destroy')(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def fill_config(spec, set_f64, set_i32):
     """Flatten a likelihood ``spec`` (nested dict, see ``desilike_amd.compile``) into config keys (include/desilike_amd.h).
 
@@ -224,8 +308,9 @@ def fill_config(spec, set_f64, set_i32):
             put(key, value)
 
 
-class Context(object):
+class Context(_Handle):
     """Owner of one ``dl_ctx`` (device constants + workspaces) on one GPU."""
+    _prefix = 'dl'
 
     def __init__(self, spec, device=0):
         lib = load()
@@ -242,13 +327,10 @@ class Context(object):
 
         try:
             fill_config(spec, set_f64, set_i32)
-            handle = ctypes.c_void_p()
-            rc = lib.dl_create(ctypes.byref(handle), int(device), cfg)
+            self._create(int(device), cfg)
         finally:
             lib.dl_config_free(cfg)
-        if rc != 0:
-            raise LibraryError(lib.dl_last_error(None).decode())
-        self._lib, self._handle, self.device = lib, handle, int(device)
+        self.device = int(device)
         self.n_params, self.n_data, self.n_obs, self.n_solved = (self.info(name) for name in ['n_params', 'n_data', 'n_obs', 'n_solved'])
         # parameters derived from others by an expression (parameter.py:758-807) are extra theta columns of the device context, computed here from the caller's
         # columns: ``expand(theta [B, n_params]) -> [B, n_device_params]`` (numpy array or torch tensor, whatever it is given), set by the likelihood
@@ -280,23 +362,9 @@ class Context(object):
             self._expanded = theta    # alive until the next call on this context (calls on one context are serialised: include/desilike_amd.h)
         return theta
 
-    def info(self, key):
-        return int(self._lib.dl_info(self._handle, key.encode()))
-
-    def _check(self, rc):
+    def _check(self, rc):      # (a context keeps its own last message)
         if rc != 0:
             raise LibraryError(self._lib.dl_last_error(self._handle).decode())
-
-    def close(self):
-        if getattr(self, '_handle', None):
-            self._lib.dl_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- host-pointer entry points (numpy in / numpy out) ----
     def eval_batch_host(self, theta, return_flattheory=False, return_solved=False):
@@ -533,21 +601,18 @@ class Context(object):
                     samples_per_kernel=dict(theory=int(ms[6]), window_gemm=int(ms[7]), finalize=int(ms[8])))
 
 
-class FFTLogPlan(object):
+class FFTLogPlan(_Handle):
     """Owner of one ``dl_fftlog`` plan (include/desilike_amd.h): batched FFTLog Hankel transform of ``fun [B, n_ell, n]`` on one GPU."""
+    _prefix = 'dl_fftlog'
 
     def __init__(self, n, npad, pre, u, post, device=0):
-        lib = load()
         pre = np.ascontiguousarray(pre, dtype='f8')
         u = np.ascontiguousarray(u, dtype='f8')          # [n_ell, npad // 2 + 1, 2]
         post = np.ascontiguousarray(post, dtype='f8')    # [n_ell, n]
         self.n, self.npad, self.n_ell, self.device = int(n), int(npad), int(post.shape[0]), int(device)
         if pre.shape != (self.n,) or u.shape != (self.n_ell, self.npad // 2 + 1, 2) or post.shape != (self.n_ell, self.n):
             raise ValueError('inconsistent FFTLog plan arrays: pre {}, u {}, post {}'.format(pre.shape, u.shape, post.shape))
-        handle = ctypes.c_void_p()
-        if lib.dl_fftlog_create(ctypes.byref(handle), self.device, self.n, self.npad, self.n_ell, _f64_ptr(pre), _f64_ptr(u), _f64_ptr(post)) != 0:
-            raise LibraryError(lib.dl_last_error(None).decode())
-        self._lib, self._handle = lib, handle
+        self._create(self.device, self.n, self.npad, self.n_ell, _f64_ptr(pre), _f64_ptr(u), _f64_ptr(post))
 
     def apply(self, fun, out=None, stream=None):
         """``fun``: contiguous float64 CUDA(ROCm) tensor [B, n_ell, n] on this plan's device; returns ``out`` (allocated if None); asynchronous on ``stream``."""
@@ -556,47 +621,20 @@ class FFTLogPlan(object):
         if out is None: out = torch.empty_like(fun)
         assert out.is_contiguous() and out.dtype == torch.float64 and out.shape == fun.shape and out.device == fun.device
         if stream is None: stream = torch.cuda.current_stream(fun.device).cuda_stream
-        if self._lib.dl_fftlog_apply(self._handle, ctypes.c_void_p(fun.data_ptr()), fun.shape[0], ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)) != 0:
-            raise LibraryError(self._lib.dl_last_error(None).decode())
+        self._check(self._lib.dl_fftlog_apply(self._handle, ctypes.c_void_p(fun.data_ptr()), fun.shape[0], ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)))
         return out
 
-    def close(self):
-        if getattr(self, '_handle', None):
-            self._lib.dl_fftlog_destroy(self._handle)
-            self._handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceEnsemble(object):
+class DeviceEnsemble(_Handle):
     """Owner of one ``dl_ensemble`` (include/desilike_amd.h): affine-invariant ensemble sampler resident on the GPU of ``ctx``; ``group``: an
     :class:`desilike_amd.parallel.RcclGroup` to shard every half-step's proposals over the ranks (or ``None``)."""
+    _prefix = 'dl_ensemble'
 
     def __init__(self, ctx, nwalkers, a=2., seed=0, offset=0., group=None):
-        lib = load()
-        if ctx.expand is not None:
-            raise NotImplementedError('the device-resident ensemble proposes in the columns of the device context: parameters derived by an expression need the host-driven sampler')
-        handle = ctypes.c_void_p()
-        comm = getattr(group, 'handle', None)
-        if lib.dl_ensemble_create(ctypes.byref(handle), ctx._handle, int(nwalkers), float(a), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), float(offset), comm) != 0:
-            raise LibraryError(lib.dl_last_error(None).decode())
-        self._lib, self._handle, self._ctx, self._group = lib, handle, ctx, group   # (the context and the group must outlive the ensemble)
+        _refuse_expand(ctx, 'ensemble proposes')
+        self._create(ctx._handle, int(nwalkers), float(a), _seed(seed), float(offset), getattr(group, 'handle', None))
+        self._ctx, self._group = ctx, group   # (the context and the group must outlive the ensemble)
         self.nwalkers, self.n_params, self.device = int(nwalkers), ctx.n_params, ctx.device
-
-    def _check(self, rc):
-        if rc != 0:
-            raise LibraryError(self._lib.dl_last_error(None).decode())
-
-    def info(self, key):
-        return int(self._lib.dl_ensemble_info(self._handle, key.encode()))
-
-    def _stream(self, stream):
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(torch.device('cuda', self.device)).cuda_stream if stream is None else stream)
 
     def set_state(self, coords, logposterior=None, stream=None):
         coords = np.ascontiguousarray(coords, dtype='f8')
@@ -609,12 +647,10 @@ class DeviceEnsemble(object):
 
     def set_counter(self, iteration, naccepted=None, stream=None):
         """Resume: iteration counter of the counter-based generator (and accepted counts per walker)."""
-        nacc = None
         if naccepted is not None:
             naccepted = np.ascontiguousarray(naccepted, dtype='i8')
             if naccepted.shape != (self.nwalkers,): raise ValueError('naccepted must have shape ({:d},)'.format(self.nwalkers))
-            nacc = naccepted.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-        self._check(self._lib.dl_ensemble_set_counter(self._handle, int(iteration), nacc, self._stream(stream)))
+        self._check(self._lib.dl_ensemble_set_counter(self._handle, int(iteration), _ptr(naccepted), self._stream(stream)))
 
     def run(self, niterations, thin_by=1, chain=None, chain_logp=None, stream=None):
         """Enqueue ``niterations`` ensemble updates (asynchronous); ``chain [niterations // thin_by, nwalkers, P]`` / ``chain_logp [niterations // thin_by, nwalkers]``:
@@ -634,36 +670,23 @@ class DeviceEnsemble(object):
         """(coords [nwalkers, P], logposterior [nwalkers], naccepted [nwalkers]) as numpy arrays; synchronises the stream."""
         coords, logp = np.empty((self.nwalkers, self.n_params), dtype='f8'), np.empty(self.nwalkers, dtype='f8')
         nacc = np.empty(self.nwalkers, dtype='i8')
-        self._check(self._lib.dl_ensemble_get_state(self._handle, _f64_ptr(coords), _f64_ptr(logp), nacc.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self._stream(stream)))
+        self._check(self._lib.dl_ensemble_get_state(self._handle, _f64_ptr(coords), _f64_ptr(logp), _ptr(nacc), self._stream(stream)))
         return coords, logp, nacc
 
-    def close(self):
-        if getattr(self, '_handle', None):
-            self._lib.dl_ensemble_destroy(self._handle)
-            self._handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class CovariancePlan(object):
+class CovariancePlan(_Handle):
     """Owner of one ``dl_cov`` plan (include/desilike_amd.h): Gaussian covariance of multipole observables from theory spectra resident on the GPU.  ``arrays``: dict with the
     plan's host arrays (built by ``desilike_amd.observables.galaxy_clustering.covariance``)."""
+    _prefix = 'dl_cov'
 
     def __init__(self, n, n_ell, n_k, ell0, shotnoise, cell_i, cell_d, pt_i, pt_d, gtab, sym, device=0):
-        lib = load()
         n_ell, n_k, ell0 = (np.ascontiguousarray(a, dtype=np.int32) for a in (n_ell, n_k, ell0))
         shotnoise = np.ascontiguousarray(shotnoise, dtype='f8')
         cell_i, pt_i, sym = (np.ascontiguousarray(a, dtype=np.int32) for a in (np.reshape(cell_i, (-1, 8)), np.reshape(pt_i, (-1, 2)), np.reshape(sym, (-1, 2))))
         cell_d, pt_d, gtab = (np.ascontiguousarray(a, dtype='f8') for a in (np.reshape(cell_d, (-1, 4)), np.reshape(pt_d, (-1, 6)), np.reshape(gtab, (-1, 5, 5))))
-        handle = ctypes.c_void_p()
-        if lib.dl_cov_create(ctypes.byref(handle), int(device), int(n), len(n_ell), _i32_ptr(n_ell), _i32_ptr(n_k), _i32_ptr(ell0), _f64_ptr(shotnoise), len(cell_i), _i32_ptr(cell_i),
-                             _f64_ptr(cell_d), len(pt_i), _i32_ptr(pt_i), _f64_ptr(pt_d), len(gtab), _f64_ptr(gtab), len(sym), _i32_ptr(sym)) != 0:
-            raise LibraryError(lib.dl_last_error(None).decode())
-        self._lib, self._handle, self.device, self.n, self.shapes = lib, handle, int(device), int(n), [(int(a), int(b)) for a, b in zip(n_ell, n_k)]
+        self._create(int(device), int(n), len(n_ell), _i32_ptr(n_ell), _i32_ptr(n_k), _i32_ptr(ell0), _f64_ptr(shotnoise), len(cell_i), _i32_ptr(cell_i), _f64_ptr(cell_d), len(pt_i),
+                     _i32_ptr(pt_i), _f64_ptr(pt_d), len(gtab), _f64_ptr(gtab), len(sym), _i32_ptr(sym))
+        self.device, self.n, self.shapes = int(device), int(n), [(int(a), int(b)) for a, b in zip(n_ell, n_k)]
 
     def apply(self, powers, out=None, stream=None):
         """``powers``: one float64 device tensor ``[B, n_ell, n_k]`` per theory; returns the covariance matrices ``[B, n, n]`` (device tensor; asynchronous)."""
@@ -675,43 +698,21 @@ class CovariancePlan(object):
         assert out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (B, self.n, self.n)
         if stream is None: stream = torch.cuda.current_stream(powers[0].device).cuda_stream
         ptrs = (ctypes.c_void_p * len(powers))(*[power.data_ptr() for power in powers])
-        if self._lib.dl_cov_apply(self._handle, ptrs, B, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)) != 0:
-            raise LibraryError(self._lib.dl_last_error(None).decode())
+        self._check(self._lib.dl_cov_apply(self._handle, ptrs, B, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)))
         return out
 
-    def close(self):
-        if getattr(self, '_handle', None):
-            self._lib.dl_cov_destroy(self._handle)
-            self._handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class MLPTrainer(object):
+class MLPTrainer(_Handle):
     """Owner of one ``dl_mlp`` (include/desilike_amd.h): fp64 Adam training of a dense network on one GPU.  ``layers``: list of (kernel [n_in, n_out], bias [n_out])
     initial values; ``activation``: 'silu' / 'relu' / 'tanh'."""
+    _prefix = 'dl_mlp'
 
     def __init__(self, layers, activation='silu', device=0):
-        lib = load()
         self.shapes = [(np.shape(kernel), np.shape(bias)) for kernel, bias in layers]
         widths = np.array([self.shapes[0][0][0]] + [shape[0][1] for shape in self.shapes], dtype=np.int32)
         flat = np.ascontiguousarray(np.concatenate([np.concatenate([np.ravel(kernel), np.ravel(bias)]) for kernel, bias in layers]), dtype='f8')
-        handle = ctypes.c_void_p()
-        if lib.dl_mlp_create(ctypes.byref(handle), int(device), len(layers), _i32_ptr(widths), {'silu': 0, 'relu': 1, 'tanh': 2}[activation], _f64_ptr(flat)) != 0:
-            raise LibraryError(lib.dl_last_error(None).decode())
-        self._lib, self._handle, self.device = lib, handle, int(device)
-        self.n_weights = int(lib.dl_mlp_info(handle, b'n_weights'))
-
-    def _check(self, rc):
-        if rc != 0: raise LibraryError(self._lib.dl_last_error(None).decode())
-
-    def _stream(self, stream):
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(torch.device('cuda', self.device)).cuda_stream if stream is None else stream)
+        self._create(int(device), len(layers), _i32_ptr(widths), {'silu': 0, 'relu': 1, 'tanh': 2}[activation], _f64_ptr(flat))
+        self.device, self.n_weights = int(device), self.info('n_weights')
 
     def train(self, x, y, batch, nsteps, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, return_loss=True, stream=None):
         """``nsteps`` Adam steps on consecutive chunks of ``batch`` rows of the device tensors ``x [S, n_in]``, ``y [S, n_out]``; returns the batch losses [nsteps]."""
@@ -729,7 +730,7 @@ class MLPTrainer(object):
 
     def forward(self, x, stream=None):
         import torch
-        out = torch.empty((x.shape[0], int(self._lib.dl_mlp_info(self._handle, b'n_out'))), dtype=torch.float64, device=x.device)
+        out = torch.empty((x.shape[0], self.info('n_out')), dtype=torch.float64, device=x.device)
         self._check(self._lib.dl_mlp_forward(self._handle, ctypes.c_void_p(x.data_ptr()), x.shape[0], ctypes.c_void_p(out.data_ptr()), self._stream(stream)))
         return out
 
@@ -744,26 +745,15 @@ class MLPTrainer(object):
             off += nk + nb
         return out
 
-    def close(self):
-        if getattr(self, '_handle', None):
-            self._lib.dl_mlp_destroy(self._handle)
-            self._handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceMH(object):
+class DeviceMH(_Handle):
     """Owner of one ``dl_mh`` (include/desilike_amd.h): ``nchains`` blocked Metropolis-Hastings chains x ``vectorize`` speculative proposals per try, resident on the
     GPU of ``ctx``.  ``order``: sorted (block) position -> column of the context; ``blocks`` / ``oversample``: block sizes (slowest first) and oversampling factors."""
 
+    _prefix = 'dl_mh'
+
     def __init__(self, ctx, nchains, vectorize=1, blocks=None, oversample=None, order=None, chain_ids=None, proposal_scale=2.4, seed=0, offset=0., max_tries=1000):
-        lib = load()
-        if ctx.expand is not None:
-            raise NotImplementedError('the device-resident sampler proposes in the columns of the device context: parameters derived by an expression need the host-driven sampler')
+        _refuse_expand(ctx, 'sampler proposes')
         P = ctx.n_params
         blocks = np.ascontiguousarray([P] if blocks is None else blocks, dtype='i4')
         oversample = np.ascontiguousarray(np.ones(len(blocks)) if oversample is None else oversample, dtype='i4')
@@ -771,24 +761,10 @@ class DeviceMH(object):
         chain_ids = np.ascontiguousarray(np.arange(nchains) if chain_ids is None else chain_ids, dtype='i4')
         if len(oversample) != len(blocks) or len(order) != P or len(chain_ids) != nchains:
             raise ValueError('blocks / oversample / order / chain_ids have inconsistent sizes')
-        i32 = ctypes.POINTER(ctypes.c_int32)
-        handle = ctypes.c_void_p()
-        if lib.dl_mh_create(ctypes.byref(handle), ctx._handle, int(nchains), int(vectorize), chain_ids.ctypes.data_as(i32), order.ctypes.data_as(i32), blocks.ctypes.data_as(i32),
-                            oversample.ctypes.data_as(i32), len(blocks), float(proposal_scale), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), float(offset), int(max_tries)) != 0:
-            raise LibraryError(lib.dl_last_error(None).decode())
-        self._lib, self._handle, self._ctx = lib, handle, ctx     # (the context must outlive the sampler)
+        self._create(ctx._handle, int(nchains), int(vectorize), _ptr(chain_ids), _ptr(order), _ptr(blocks), _ptr(oversample), len(blocks), float(proposal_scale), _seed(seed),
+                     float(offset), int(max_tries))
+        self._ctx = ctx     # (the context must outlive the sampler)
         self.nchains, self.vectorize, self.n_params, self.device = int(nchains), int(vectorize), P, ctx.device
-
-    def _check(self, rc):
-        if rc != 0:
-            raise LibraryError(self._lib.dl_last_error(None).decode())
-
-    def info(self, key):
-        return int(self._lib.dl_mh_info(self._handle, key.encode()))
-
-    def _stream(self, stream):
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(torch.device('cuda', self.device)).cuda_stream if stream is None else stream)
 
     def set_covariance(self, cholesky, stream=None):
         """Lower-triangular Cholesky factor [P, P] of the proposal covariance, parameters in sorted (block) order."""
@@ -800,7 +776,6 @@ class DeviceMH(object):
         coords = np.ascontiguousarray(coords, dtype='f8')
         if coords.shape != (self.nchains, self.n_params):
             raise ValueError('coords must have shape ({:d}, {:d}), found {}'.format(self.nchains, self.n_params, coords.shape))
-        i64 = ctypes.POINTER(ctypes.c_int64)
 
         def vector(values, dtype):
             if values is None: return None
@@ -809,19 +784,14 @@ class DeviceMH(object):
             return values
 
         logposterior, weight, naccepted = vector(logposterior, 'f8'), vector(weight, 'i8'), vector(naccepted, 'i8')
-        self._check(self._lib.dl_mh_set_state(self._handle, _f64_ptr(coords), _f64_ptr(logposterior), None if weight is None else weight.ctypes.data_as(i64),
-                                              None if naccepted is None else naccepted.ctypes.data_as(i64), int(tries), self._stream(stream)))
+        self._check(self._lib.dl_mh_set_state(self._handle, _f64_ptr(coords), _f64_ptr(logposterior), _ptr(weight), _ptr(naccepted), int(tries), self._stream(stream)))
 
     def run(self, ntries, thin_by=1, stream=None):
         """Enqueue ``ntries`` tries of every chain (asynchronous); returns the device tensors (coords [nchains, ntries, P], logposterior [nchains, ntries],
         weight [nchains, ntries], count [nchains]) that hold the ``count`` states recorded by this call once the stream has run."""
-        import torch
-        device = torch.device('cuda', self.device)
         ntries = int(ntries)
-        coords = torch.empty((self.nchains, max(ntries, 1), self.n_params), dtype=torch.float64, device=device)
-        logp = torch.empty((self.nchains, max(ntries, 1)), dtype=torch.float64, device=device)
-        weight = torch.empty((self.nchains, max(ntries, 1)), dtype=torch.int64, device=device)
-        count = torch.zeros(self.nchains, dtype=torch.int32, device=device)
+        C, n, P = self.nchains, max(ntries, 1), self.n_params
+        coords, logp, weight, count = _record_buffers(self.device, [('f8', (C, n, P), None), ('f8', (C, n), None), ('i8', (C, n), None), ('i4', (C,), 0)])
         self._check(self._lib.dl_mh_run(self._handle, ntries, int(thin_by), ctypes.c_void_p(coords.data_ptr()), ctypes.c_void_p(logp.data_ptr()), ctypes.c_void_p(weight.data_ptr()),
                                         ctypes.c_void_p(count.data_ptr()), self._stream(stream)))
         return coords, logp, weight, count
@@ -830,54 +800,23 @@ class DeviceMH(object):
         """(coords [nchains, P], logposterior, weight, naccepted, consecutive failed tries) as numpy arrays; synchronises the stream."""
         coords, logp = np.empty((self.nchains, self.n_params), dtype='f8'), np.empty(self.nchains, dtype='f8')
         weight, nacc, fails = np.empty(self.nchains, dtype='i8'), np.empty(self.nchains, dtype='i8'), np.empty(self.nchains, dtype='i4')
-        i64 = ctypes.POINTER(ctypes.c_int64)
-        self._check(self._lib.dl_mh_get_state(self._handle, _f64_ptr(coords), _f64_ptr(logp), weight.ctypes.data_as(i64), nacc.ctypes.data_as(i64),
-                                              fails.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self._stream(stream)))
+        self._check(self._lib.dl_mh_get_state(self._handle, _f64_ptr(coords), _f64_ptr(logp), _ptr(weight), _ptr(nacc), _ptr(fails), self._stream(stream)))
         return coords, logp, weight, nacc, fails
 
-    def close(self):
-        if getattr(self, '_handle', None):
-            self._lib.dl_mh_destroy(self._handle)
-            self._handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceNUTS(object):
+class DeviceNUTS(_Handle):
     """Owner of one ``dl_nuts`` (include/desilike_amd.h): ``nchains`` No-U-Turn chains resident on the GPU of ``ctx``, advanced one leapfrog step per call of the
     gradient.  ``gradient``: 'auto', 'analytic' or 'finite'; ``fd_delta`` / ``fd_limits`` [P, 2]: steps and prior bounds of the central differences."""
+    _prefix = 'dl_nuts'
     MODES = {'auto': 0, 'analytic': 1, 'finite': 2}
 
     def __init__(self, ctx, nchains, chain_ids=None, max_num_doublings=10, divergence_threshold=1000., seed=0, offset=0., gradient='auto', fd_delta=None, fd_limits=None):
-        lib = load()
-        if ctx.expand is not None:
-            raise NotImplementedError('the device-resident sampler moves in the columns of the device context: parameters derived by an expression need the host-driven sampler')
+        _refuse_expand(ctx)
         P = ctx.n_params
-        chain_ids = np.ascontiguousarray(np.arange(nchains) if chain_ids is None else chain_ids, dtype='i4')
-        if len(chain_ids) != nchains: raise ValueError('chain_ids must have one entry per chain')
-        fd_delta = None if fd_delta is None else np.ascontiguousarray(fd_delta, dtype='f8').reshape(P, 2)
-        fd_limits = None if fd_limits is None else np.ascontiguousarray(fd_limits, dtype='f8').reshape(P, 2)
-        handle = ctypes.c_void_p()
-        if lib.dl_nuts_create(ctypes.byref(handle), ctx._handle, int(nchains), chain_ids.ctypes.data_as(_c_int32_p), int(max_num_doublings), float(divergence_threshold),
-                              ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), float(offset), self.MODES[gradient], _f64_ptr(fd_delta), _f64_ptr(fd_limits)) != 0:
-            raise LibraryError(lib.dl_last_error(None).decode())
-        self._lib, self._handle, self._ctx = lib, handle, ctx     # (the context must outlive the sampler)
+        self._create(ctx._handle, int(nchains), _ptr(_ids(chain_ids, nchains, 'chain')), int(max_num_doublings), float(divergence_threshold), _seed(seed), float(offset),
+                     self.MODES[gradient], _ptr(_fd_table(fd_delta, P)), _ptr(_fd_table(fd_limits, P)))
+        self._ctx = ctx     # (the context must outlive the sampler)
         self.nchains, self.n_params, self.device = int(nchains), P, ctx.device
-
-    def _check(self, rc):
-        if rc != 0:
-            raise LibraryError(self._lib.dl_last_error(None).decode())
-
-    def info(self, key):
-        return int(self._lib.dl_nuts_info(self._handle, key.encode()))
-
-    def _stream(self, stream):
-        import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(torch.device('cuda', self.device)).cuda_stream if stream is None else stream)
 
     def set_mass(self, inverse_mass, step_size, stream=None):
         """Inverse mass matrix: its diagonal [P] or the matrix [P, P]; the step size of every chain."""
@@ -891,15 +830,13 @@ class DeviceNUTS(object):
             raise ValueError('coords must have shape ({:d}, {:d}), found {}'.format(self.nchains, self.n_params, coords.shape))
         logposterior = None if logposterior is None else np.ascontiguousarray(logposterior, dtype='f8').reshape(self.nchains)
         iterations = None if iterations is None else np.ascontiguousarray(iterations, dtype='i8').reshape(self.nchains)
-        self._check(self._lib.dl_nuts_set_state(self._handle, _f64_ptr(coords), _f64_ptr(logposterior), None if iterations is None else iterations.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                                self._stream(stream)))
+        self._check(self._lib.dl_nuts_set_state(self._handle, _f64_ptr(coords), _f64_ptr(logposterior), _ptr(iterations), self._stream(stream)))
 
     def get_state(self, stream=None):
         """(points [nchains, P], log-posteriors, iteration counters, log step sizes) as numpy arrays; synchronises."""
         coords, logp, logeps = np.empty((self.nchains, self.n_params)), np.empty(self.nchains), np.empty(self.nchains)
         iterations = np.empty(self.nchains, dtype='i8')
-        self._check(self._lib.dl_nuts_get_state(self._handle, _f64_ptr(coords), _f64_ptr(logp), iterations.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _f64_ptr(logeps),
-                                                self._stream(stream)))
+        self._check(self._lib.dl_nuts_get_state(self._handle, _f64_ptr(coords), _f64_ptr(logp), _ptr(iterations), _f64_ptr(logeps), self._stream(stream)))
         return coords, logp, iterations, logeps
 
     def set_adaptation(self, enabled, target_acceptance=0.8, initial_step_size=1., stream=None):
@@ -907,10 +844,8 @@ class DeviceNUTS(object):
 
     def buffers(self, quota):
         """Record buffers of one batch: coords [nchains, quota, P], logposterior [nchains, quota], info [nchains, quota, 5], count [nchains] (zeroed)."""
-        import torch
-        device = torch.device('cuda', self.device)
-        return (torch.empty((self.nchains, quota, self.n_params), dtype=torch.float64, device=device), torch.empty((self.nchains, quota), dtype=torch.float64, device=device),
-                torch.empty((self.nchains, quota, 5), dtype=torch.float64, device=device), torch.zeros(self.nchains, dtype=torch.int32, device=device))
+        C, P = self.nchains, self.n_params
+        return _record_buffers(self.device, [('f8', (C, quota, P), None), ('f8', (C, quota), None), ('f8', (C, quota, 5), None), ('i4', (C,), 0)])
 
     def run(self, nsteps, quota, buffers, thin_by=1, stream=None):
         """Enqueue ``nsteps`` leapfrog steps of every chain into the record ``buffers`` of a batch of ``quota`` records per chain (asynchronous)."""
@@ -918,47 +853,24 @@ class DeviceNUTS(object):
         self._check(self._lib.dl_nuts_run(self._handle, int(nsteps), int(quota), int(thin_by), ctypes.c_void_p(coords.data_ptr()), ctypes.c_void_p(logp.data_ptr()),
                                           ctypes.c_void_p(info.data_ptr()), ctypes.c_void_p(count.data_ptr()), self._stream(stream)))
 
-    def close(self):
-        if getattr(self, '_handle', None):
-            self._lib.dl_nuts_destroy(self._handle)
-            self._handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceMCLMC(object):
+class DeviceMCLMC(_Handle):
     """Owner of one ``dl_mclmc`` (include/desilike_amd.h): ``nchains`` microcanonical Langevin chains resident on the GPU of ``ctx``, one (isokinetic_leapfrog) or two
     (isokinetic_mclachlan) gradient batches per step.  ``gradient``, ``fd_delta``, ``fd_limits`` as :class:`DeviceNUTS`."""
+    _prefix = 'dl_mclmc'
     MODES = DeviceNUTS.MODES
     INTEGRATORS = {'isokinetic_leapfrog': 0, 'isokinetic_mclachlan': 1}
 
     def __init__(self, ctx, nchains, chain_ids=None, integrator='isokinetic_mclachlan', seed=0, offset=0., gradient='auto', fd_delta=None, fd_limits=None):
-        lib = load()
-        if ctx.expand is not None:
-            raise NotImplementedError('the device-resident sampler moves in the columns of the device context: parameters derived by an expression need the host-driven sampler')
+        _refuse_expand(ctx)
         if isinstance(integrator, str):
             if integrator not in self.INTEGRATORS: raise ValueError('integrator must be one of {}, found {!r}'.format(sorted(self.INTEGRATORS), integrator))
             integrator = self.INTEGRATORS[integrator]
         P = ctx.n_params
-        chain_ids = np.ascontiguousarray(np.arange(nchains) if chain_ids is None else chain_ids, dtype='i4')
-        if len(chain_ids) != nchains: raise ValueError('chain_ids must have one entry per chain')
-        fd_delta = None if fd_delta is None else np.ascontiguousarray(fd_delta, dtype='f8').reshape(P, 2)
-        fd_limits = None if fd_limits is None else np.ascontiguousarray(fd_limits, dtype='f8').reshape(P, 2)
-        handle = ctypes.c_void_p()
-        if lib.dl_mclmc_create(ctypes.byref(handle), ctx._handle, int(nchains), chain_ids.ctypes.data_as(_c_int32_p), int(integrator), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                               float(offset), self.MODES[gradient], _f64_ptr(fd_delta), _f64_ptr(fd_limits)) != 0:
-            raise LibraryError(lib.dl_last_error(None).decode())
-        self._lib, self._handle, self._ctx = lib, handle, ctx     # (the context must outlive the sampler)
+        self._create(ctx._handle, int(nchains), _ptr(_ids(chain_ids, nchains, 'chain')), int(integrator), _seed(seed), float(offset), self.MODES[gradient],
+                     _ptr(_fd_table(fd_delta, P)), _ptr(_fd_table(fd_limits, P)))
+        self._ctx = ctx     # (the context must outlive the sampler)
         self.nchains, self.n_params, self.device = int(nchains), P, ctx.device
-
-    _check, _stream = DeviceNUTS._check, DeviceNUTS._stream
-
-    def info(self, key):
-        return int(self._lib.dl_mclmc_info(self._handle, key.encode()))
 
     def set_preconditioner(self, factor, stream=None):
         """A of x = x^ + A z: its diagonal [P] or a lower triangular factor [P, P]."""
@@ -976,15 +888,13 @@ class DeviceMCLMC(object):
         momenta = None if momenta is None else np.ascontiguousarray(momenta, dtype='f8').reshape(self.nchains, self.n_params)
         logposterior = None if logposterior is None else np.ascontiguousarray(logposterior, dtype='f8').reshape(self.nchains)
         counters = None if counters is None else np.ascontiguousarray(counters, dtype='i8').reshape(self.nchains)
-        self._check(self._lib.dl_mclmc_set_state(self._handle, _f64_ptr(coords), _f64_ptr(momenta), _f64_ptr(logposterior),
-                                                 None if counters is None else counters.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self._stream(stream)))
+        self._check(self._lib.dl_mclmc_set_state(self._handle, _f64_ptr(coords), _f64_ptr(momenta), _f64_ptr(logposterior), _ptr(counters), self._stream(stream)))
 
     def get_state(self, stream=None):
         """(points [nchains, P], momenta [nchains, P], log-posteriors, step counters, step sizes) as numpy arrays; synchronises."""
         coords, momenta = np.empty((self.nchains, self.n_params)), np.empty((self.nchains, self.n_params))
         logp, eps, counters = np.empty(self.nchains), np.empty(self.nchains), np.empty(self.nchains, dtype='i8')
-        self._check(self._lib.dl_mclmc_get_state(self._handle, _f64_ptr(coords), _f64_ptr(momenta), _f64_ptr(logp), counters.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                                 _f64_ptr(eps), self._stream(stream)))
+        self._check(self._lib.dl_mclmc_get_state(self._handle, _f64_ptr(coords), _f64_ptr(momenta), _f64_ptr(logp), _ptr(counters), _f64_ptr(eps), self._stream(stream)))
         return coords, momenta, logp, counters, eps
 
     def set_adaptation(self, step_size_on, moments_on=False, desired_energy_var=5e-4, trust_in_estimate=1.5, num_effective_samples=150., stream=None):
@@ -999,10 +909,8 @@ class DeviceMCLMC(object):
 
     def buffers(self, quota):
         """Record buffers of one batch: coords [nchains, quota, P], logposterior [nchains, quota], info [nchains, quota, 3], count [nchains] (zeroed)."""
-        import torch
-        device = torch.device('cuda', self.device)
-        return (torch.empty((self.nchains, quota, self.n_params), dtype=torch.float64, device=device), torch.empty((self.nchains, quota), dtype=torch.float64, device=device),
-                torch.empty((self.nchains, quota, 3), dtype=torch.float64, device=device), torch.zeros(self.nchains, dtype=torch.int32, device=device))
+        C, P = self.nchains, self.n_params
+        return _record_buffers(self.device, [('f8', (C, quota, P), None), ('f8', (C, quota), None), ('f8', (C, quota, 3), None), ('i4', (C,), 0)])
 
     def run(self, nsteps, quota, buffers, thin_by=1, stream=None):
         """Enqueue ``nsteps`` integrator steps of every chain into the record ``buffers`` of a batch of ``quota`` records per chain (asynchronous)."""
@@ -1010,41 +918,19 @@ class DeviceMCLMC(object):
         self._check(self._lib.dl_mclmc_run(self._handle, int(nsteps), int(quota), int(thin_by), ctypes.c_void_p(coords.data_ptr()), ctypes.c_void_p(logp.data_ptr()),
                                            ctypes.c_void_p(info.data_ptr()), ctypes.c_void_p(count.data_ptr()), self._stream(stream)))
 
-    def close(self):
-        if getattr(self, '_handle', None):
-            self._lib.dl_mclmc_destroy(self._handle)
-            self._handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceSMC(object):
+class DeviceSMC(_Handle):
     """Owner of one ``dl_smc`` (include/desilike_amd.h): ``nsystems`` independent systems of ``nparticles`` particles of tempered sequential Monte Carlo resident on the
     GPU of ``ctx``; ``widths`` [P]: the width or scale of every parameter's prior."""
+    _prefix = 'dl_smc'
 
     def __init__(self, ctx, nsystems, nparticles, widths, system_ids=None, seed=0, offset=0.):
-        lib = load()
-        if ctx.expand is not None:
-            raise NotImplementedError('the device-resident sampler moves in the columns of the device context: parameters derived by an expression need the host-driven sampler')
+        _refuse_expand(ctx)
         P = ctx.n_params
-        system_ids = np.ascontiguousarray(np.arange(nsystems) if system_ids is None else system_ids, dtype='i4')
-        if len(system_ids) != nsystems: raise ValueError('system_ids must have one entry per system')
-        widths = np.ascontiguousarray(widths, dtype='f8').reshape(P)
-        handle = ctypes.c_void_p()
-        if lib.dl_smc_create(ctypes.byref(handle), ctx._handle, int(nsystems), int(nparticles), system_ids.ctypes.data_as(_c_int32_p), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                             float(offset), _f64_ptr(widths)) != 0:
-            raise LibraryError(lib.dl_last_error(None).decode())
-        self._lib, self._handle, self._ctx = lib, handle, ctx     # (the context must outlive the sampler)
+        self._create(ctx._handle, int(nsystems), int(nparticles), _ptr(_ids(system_ids, nsystems, 'system')), _seed(seed), float(offset),
+                     _ptr(np.ascontiguousarray(widths, dtype='f8').reshape(P)))
+        self._ctx = ctx     # (the context must outlive the sampler)
         self.nsystems, self.nparticles, self.n_params, self.device, self.n_steps = int(nsystems), int(nparticles), P, ctx.device, 0
-
-    _check, _stream = DeviceNUTS._check, DeviceNUTS._stream
-
-    def info(self, key):
-        return int(self._lib.dl_smc_info(self._handle, key.encode()))
 
     def set_hyper(self, ess_fraction, n_steps, target_acceptance, scale=1., stream=None):
         self._check(self._lib.dl_smc_set_hyper(self._handle, float(ess_fraction), int(n_steps), float(target_acceptance), float(scale), self._stream(stream)))
@@ -1056,22 +942,20 @@ class DeviceSMC(object):
             raise ValueError('coords must have shape ({:d}, {:d}, {:d}), found {}'.format(self.nsystems, self.nparticles, self.n_params, coords.shape))
         self._check(self._lib.dl_smc_set_particles(self._handle, _f64_ptr(coords), self._stream(stream)))
 
-    def _shapes(self):
+    def _state_table(self):
+        """(dtype, shape) of every array of the state, in the order of ``dl_smc_set_state`` / ``dl_smc_get_state``."""
         K, N, P = self.nsystems, self.nparticles, self.n_params
-        return [(K, N, P), (K, N), (K, N), (K,), (K,), (K,), (K,), (K, P, P)]
+        return [('f8', (K, N, P)), ('f8', (K, N)), ('f8', (K, N)), ('f8', (K,)), ('f8', (K,)), ('i8', (K,)), ('f8', (K,)), ('f8', (K, P, P))]
 
     def set_state(self, coords, loglike, logprior, beta, logz, counters, scale, factor, stream=None):
         """What :meth:`get_state` returns."""
-        arrays = [np.ascontiguousarray(a, dtype='i8' if i == 5 else 'f8').reshape(shape) for i, (a, shape) in enumerate(zip([coords, loglike, logprior, beta, logz, counters, scale, factor],
-                                                                                                                      self._shapes()))]
-        args = [a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if i == 5 else _f64_ptr(a) for i, a in enumerate(arrays)]
-        self._check(self._lib.dl_smc_set_state(self._handle, *args, self._stream(stream)))
+        arrays = _state_in([coords, loglike, logprior, beta, logz, counters, scale, factor], self._state_table())
+        self._check(self._lib.dl_smc_set_state(self._handle, *[_ptr(a) for a in arrays], self._stream(stream)))
 
     def get_state(self, stream=None):
         """(coords [K, N, P], loglike [K, N], logprior [K, N], beta, logz (without the offset), counters, scale [K], factor [K, P, P]) as numpy arrays; synchronises."""
-        arrays = [np.empty(shape, dtype='i8' if i == 5 else 'f8') for i, shape in enumerate(self._shapes())]
-        args = [a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if i == 5 else _f64_ptr(a) for i, a in enumerate(arrays)]
-        self._check(self._lib.dl_smc_get_state(self._handle, *args, self._stream(stream)))
+        arrays = _state_out(self._state_table())
+        self._check(self._lib.dl_smc_get_state(self._handle, *[_ptr(a) for a in arrays], self._stream(stream)))
         return tuple(arrays)
 
     def get_decisions(self, stream=None):
@@ -1084,11 +968,8 @@ class DeviceSMC(object):
 
     def buffers(self, quota):
         """Record buffers of one batch: history [K, quota, 5], coords [K, quota, N, P], logposterior [K, quota, N], count [K, 2] (zeroed)."""
-        import torch
-        device = torch.device('cuda', self.device)
         K, N, P = self.nsystems, self.nparticles, self.n_params
-        return (torch.zeros((K, quota, 5), dtype=torch.float64, device=device), torch.empty((K, quota, N, P), dtype=torch.float64, device=device),
-                torch.empty((K, quota, N), dtype=torch.float64, device=device), torch.zeros((K, 2), dtype=torch.int32, device=device))
+        return _record_buffers(self.device, [('f8', (K, quota, 5), 0), ('f8', (K, quota, N, P), None), ('f8', (K, quota, N), None), ('i4', (K, 2), 0)])
 
     def run(self, niterations, quota, buffers, stream=None):
         """Enqueue ``niterations`` iterations of every system into the record ``buffers`` of a batch of ``quota`` records per system (asynchronous)."""
@@ -1096,42 +977,18 @@ class DeviceSMC(object):
         self._check(self._lib.dl_smc_run(self._handle, int(niterations), int(quota), ctypes.c_void_p(history.data_ptr()), ctypes.c_void_p(coords.data_ptr()),
                                          ctypes.c_void_p(logp.data_ptr()), ctypes.c_void_p(count.data_ptr()), self._stream(stream)))
 
-    def close(self):
-        if getattr(self, '_handle', None):
-            self._lib.dl_smc_destroy(self._handle)
-            self._handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceNested(object):
+class DeviceNested(_Handle):
     """Owner of one ``dl_nested`` (include/desilike_amd.h): ``nruns`` independent nested-sampling runs of ``nlive`` live points resident on the GPU of ``ctx``;
     ``widths`` [P]: the width or scale of every parameter's prior."""
-    _dtypes = ['f8', 'f8', 'f8', 'f8', 'f8', 'i8', 'f8', 'i4']
+    _prefix = 'dl_nested'
 
     def __init__(self, ctx, nruns, nlive, widths, run_ids=None, seed=0, offset=0.):
-        lib = load()
-        if ctx.expand is not None:
-            raise NotImplementedError('the device-resident sampler moves in the columns of the device context: parameters derived by an expression need the host-driven sampler')
+        _refuse_expand(ctx)
         P = ctx.n_params
-        run_ids = np.ascontiguousarray(np.arange(nruns) if run_ids is None else run_ids, dtype='i4')
-        if len(run_ids) != nruns: raise ValueError('run_ids must have one entry per run')
-        widths = np.ascontiguousarray(widths, dtype='f8').reshape(P)
-        handle = ctypes.c_void_p()
-        if lib.dl_nested_create(ctypes.byref(handle), ctx._handle, int(nruns), int(nlive), run_ids.ctypes.data_as(_c_int32_p), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                                float(offset), _f64_ptr(widths)) != 0:
-            raise LibraryError(lib.dl_last_error(None).decode())
-        self._lib, self._handle, self._ctx = lib, handle, ctx     # (the context must outlive the sampler)
+        self._create(ctx._handle, int(nruns), int(nlive), _ptr(_ids(run_ids, nruns, 'run')), _seed(seed), float(offset), _ptr(np.ascontiguousarray(widths, dtype='f8').reshape(P)))
+        self._ctx = ctx     # (the context must outlive the sampler)
         self.nruns, self.nlive, self.n_params, self.device, self.n_steps, self.ndelete = int(nruns), int(nlive), P, ctx.device, 0, 0
-
-    _check, _stream = DeviceNUTS._check, DeviceNUTS._stream
-
-    def info(self, key):
-        return int(self._lib.dl_nested_info(self._handle, key.encode()))
 
     def set_hyper(self, ndelete, n_steps, target_acceptance, dlogz, scale=1., stream=None):
         self._check(self._lib.dl_nested_set_hyper(self._handle, int(ndelete), int(n_steps), float(target_acceptance), float(dlogz), float(scale), self._stream(stream)))
@@ -1143,23 +1000,20 @@ class DeviceNested(object):
             raise ValueError('coords must have shape ({:d}, {:d}, {:d}), found {}'.format(self.nruns, self.nlive, self.n_params, coords.shape))
         self._check(self._lib.dl_nested_set_live(self._handle, _f64_ptr(coords), self._stream(stream)))
 
-    def _shapes(self):
+    def _state_table(self):
+        """(dtype, shape) of every array of the state, in the order of ``dl_nested_set_state`` / ``dl_nested_get_state``."""
         K, N, P = self.nruns, self.nlive, self.n_params
-        return [(K, N, P), (K, N), (K, N), (K,), (K,), (K,), (K,), (K,)]
-
-    @staticmethod
-    def _pointer(a):
-        return a.ctypes.data_as(ctypes.POINTER({'i8': ctypes.c_int64, 'i4': ctypes.c_int32}[a.dtype.str[1:]])) if a.dtype.kind == 'i' else _f64_ptr(a)
+        return [('f8', (K, N, P)), ('f8', (K, N)), ('f8', (K, N)), ('f8', (K,)), ('f8', (K,)), ('i8', (K,)), ('f8', (K,)), ('i4', (K,))]
 
     def set_state(self, coords, loglike, logprior, logx, logz, counters, scale, modes, stream=None):
         """What :meth:`get_state` returns."""
-        arrays = [np.ascontiguousarray(a, dtype=dtype).reshape(shape) for a, dtype, shape in zip([coords, loglike, logprior, logx, logz, counters, scale, modes], self._dtypes, self._shapes())]
-        self._check(self._lib.dl_nested_set_state(self._handle, *[self._pointer(a) for a in arrays], self._stream(stream)))
+        arrays = _state_in([coords, loglike, logprior, logx, logz, counters, scale, modes], self._state_table())
+        self._check(self._lib.dl_nested_set_state(self._handle, *[_ptr(a) for a in arrays], self._stream(stream)))
 
     def get_state(self, stream=None):
         """(coords [K, N, P], loglike [K, N], logprior [K, N], logx, logz (without the offset), counters, scale, modes [K]) as numpy arrays; synchronises."""
-        arrays = [np.empty(shape, dtype=dtype) for dtype, shape in zip(self._dtypes, self._shapes())]
-        self._check(self._lib.dl_nested_get_state(self._handle, *[self._pointer(a) for a in arrays], self._stream(stream)))
+        arrays = _state_out(self._state_table())
+        self._check(self._lib.dl_nested_get_state(self._handle, *[_ptr(a) for a in arrays], self._stream(stream)))
         return tuple(arrays)
 
     def get_decisions(self, stream=None):
@@ -1173,24 +1027,9 @@ class DeviceNested(object):
 
     def buffers(self, quota):
         """Record buffers of one batch: history [K, quota, 6], dead coords [K, quota, M, P], dead loglike, logprior, logweight [K, quota, M], count [K] (zeroed), modes [K]."""
-        import torch
-        device = torch.device('cuda', self.device)
         K, M, P = self.nruns, self.ndelete, self.n_params
-        dead = [torch.empty((K, quota, M), dtype=torch.float64, device=device) for _ in range(3)]
-        return (torch.zeros((K, quota, 6), dtype=torch.float64, device=device), torch.empty((K, quota, M, P), dtype=torch.float64, device=device), dead[0], dead[1], dead[2],
-                torch.zeros(K, dtype=torch.int32, device=device), torch.ones(K, dtype=torch.int32, device=device))
+        return _record_buffers(self.device, [('f8', (K, quota, 6), 0), ('f8', (K, quota, M, P), None)] + [('f8', (K, quota, M), None)] * 3 + [('i4', (K,), 0), ('i4', (K,), 1)])
 
     def run(self, niterations, quota, buffers, stream=None):
         """Enqueue ``niterations`` iterations of every run into the record ``buffers`` of a batch of ``quota`` records per run (asynchronous)."""
         self._check(self._lib.dl_nested_run(self._handle, int(niterations), int(quota), *[ctypes.c_void_p(b.data_ptr()) for b in buffers], self._stream(stream)))
-
-    def close(self):
-        if getattr(self, '_handle', None):
-            self._lib.dl_nested_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

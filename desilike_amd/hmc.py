@@ -295,12 +295,7 @@ class HMCSampler(BasePosteriorSampler):
 
     def save(self, fn=None):
         """One file per chain in the reference's checkpoint format (``Chain.save``); the hyper-parameters of the warm-up travel in the attributes ('hyp', samplers/hmc.py:196)."""
-        from .io import ChainFile
-        if fn is None: fn = self.save_fn
-        if fn is None: raise ValueError('provide a file name')
-        if isinstance(fn, str): fn = [fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-        if len(fn) != self.nchains: raise ValueError('provide one file name per chain')
+        fn = self._save_names(fn)
         if self.chain_rank != 0 or self._store is None: return
         hyp = None if self.hyp is None else {'step_size': self.hyp['step_size'], 'inverse_mass_matrix': np.asarray(self.hyp['inverse_mass_matrix']).tolist()}
-        for chain, name in zip(self.chains, fn):
-            ChainFile(dict(chain), params={param.name: param for param in self.varied_params}, attrs={'sampler': self.name, 'hyp': hyp}).save(name)
+        self._write_chains((name, chain, {'sampler': self.name, 'hyp': hyp}) for chain, name in zip(self.chains, fn))

@@ -15,7 +15,7 @@ they mean there (the engines are given diag(proposal) A and never see the centri
 import numpy as np
 
 from .nuts import NUTSSampler, _Draws
-from .samplers import CounterRNG
+from .samplers import CounterRNG, _DeviceEngine, _open_chain_files
 
 STREAM_REFRESH, STREAM_INIT = 48, 49
 INFO_FIELDS = ('energy_change', 'undone', 'step_size')
@@ -251,49 +251,15 @@ class _HostMCLMC(object):
         return tuple(np.asarray(b) for b in buffers[:3])
 
 
-class _DeviceMCLMC(object):
-    """Chains of this rank resident on the GPU (``dl_mclmc_*``)."""
-    device_resident = True
+class _DeviceMCLMC(_DeviceEngine):
+    """Chains of this rank resident on the GPU (``dl_mclmc_*``): the calls of :class:`_HostMCLMC` go to the owner ``mclmc``."""
+    _counters = ('steps',)
 
     def __init__(self, ctx, offset, chain_ids, integrator, seed, gradient, fd_delta, fd_limits):
         from ._lib import DeviceMCLMC
-        self.mclmc = DeviceMCLMC(ctx, len(chain_ids), chain_ids=chain_ids, integrator=integrator, seed=seed, offset=offset, gradient=gradient, fd_delta=fd_delta,
-                                 fd_limits=fd_limits)
+        self.mclmc = self._owner = DeviceMCLMC(ctx, len(chain_ids), chain_ids=chain_ids, integrator=integrator, seed=seed, offset=offset, gradient=gradient,
+                                               fd_delta=fd_delta, fd_limits=fd_limits)
         self.C, self.P = len(chain_ids), self.mclmc.n_params
-
-    def set_preconditioner(self, factor):
-        self.mclmc.set_preconditioner(factor)
-
-    def set_hyper(self, step_size, L):
-        self.mclmc.set_hyper(step_size, L)
-
-    def set_state(self, coords, momenta=None, logposterior=None, counters=None):
-        self.mclmc.set_state(coords, momenta=momenta, logposterior=logposterior, counters=counters)
-
-    def get_state(self):
-        return self.mclmc.get_state()
-
-    def set_adaptation(self, step_size_on, moments_on=False, desired_energy_var=5e-4, trust_in_estimate=1.5, num_effective_samples=150.):
-        self.mclmc.set_adaptation(step_size_on, moments_on, desired_energy_var, trust_in_estimate, num_effective_samples)
-
-    def get_moments(self):
-        return self.mclmc.get_moments()
-
-    def buffers(self, quota):
-        return self.mclmc.buffers(quota)
-
-    def run(self, nsteps, quota, buffers, thin_by=1):
-        self.mclmc.run(nsteps, quota, buffers, thin_by=thin_by)
-
-    def counts(self, buffers):
-        return buffers[3].cpu().numpy()        # the one synchronisation of a chunk
-
-    def records(self, buffers):
-        return tuple(b.cpu().numpy() for b in buffers[:3])
-
-    @property
-    def steps(self):
-        return self.mclmc.info('steps')
 
 
 def run_batch(engine, quota, thin_by=1, chunk=64):
@@ -481,22 +447,15 @@ class MCLMCSampler(NUTSSampler):
     def save(self, fn=None):
         """One file per chain in the reference's checkpoint format; attributes ``{'sampler': 'mclmc', 'hyp': ...}``, the chain's step counter ('iteration') and
         its momentum."""
-        from .io import ChainFile
-        if fn is None: fn = self.save_fn
-        if fn is None: raise ValueError('provide a file name')
-        if isinstance(fn, str): fn = [fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-        if len(fn) != self.nchains: raise ValueError('provide one file name per chain')
+        fn = self._save_names(fn)
         if self.chain_rank != 0 or self._store is None: return
         hyp = None if self.hyp is None else {name: (value.tolist() if isinstance(value, np.ndarray) else value) for name, value in self.hyp.items()}
-        for c, (chain, name) in enumerate(zip(self.chains, fn)):
-            attrs = {'sampler': self.name, 'hyp': hyp, 'integrator': self.mclmc_integrator, 'iteration': int(self._state[2][c]), 'seed': self.counter_seed,
-                     'momentum': self._momenta[c].tolist()}
-            ChainFile(dict(chain), params={param.name: param for param in self.varied_params}, attrs=attrs).save(name)
+        self._write_chains((name, chain, {'sampler': self.name, 'hyp': hyp, 'integrator': self.mclmc_integrator, 'iteration': int(self._state[2][c]), 'seed': self.counter_seed,
+                                          'momentum': self._momenta[c].tolist()}) for c, (chain, name) in enumerate(zip(self.chains, fn)))
 
     def _resume(self, sources):
         """Continue the chains saved by :meth:`save`: last points, momenta, step counters, hyper-parameters (no new warm-up)."""
-        from .io import ChainFile
-        files = [s if hasattr(s, 'arrays') else ChainFile.load(s) for s in sources]
+        files = _open_chain_files(sources)
         names = self.varied_params.names()
         points = np.array([[np.asarray(f.arrays[name], dtype='f8').ravel()[-1] for name in names] for f in files])
         logp = np.array([np.asarray(f.arrays['logposterior'], dtype='f8').ravel()[-1] for f in files])

@@ -12,7 +12,7 @@ import sys
 
 import numpy as np
 
-from .samplers import BasePosteriorSampler, CounterRNG, _batch_iterate
+from .samplers import BasePosteriorSampler, CounterRNG, _batch_iterate, _chain_file_names, _open_chain_files, _parse_chains
 from .parallel import WalkerSharding
 
 
@@ -342,19 +342,12 @@ class MCMCSampler(BasePosteriorSampler):
         self.sorted_names = [name for group in groups for name in group]
         self.order = np.array([names.index(name) for name in self.sorted_names], dtype='i4')       # sorted position -> column of the likelihood's varied parameters
         self.proposal_scale = float(proposal_scale)
-        resume = None
-        if not isinstance(chains, (int, np.integer)):
-            resume = [chains] if isinstance(chains, (str, dict)) or hasattr(chains, 'arrays') else list(chains)
-            chains = len(resume)
-        self.nchains = int(chains)
-        if self.nchains < 1: raise ValueError('chains must be >= 1')
+        self.nchains, resume = _parse_chains(chains)
         self.chain_group = self.sharding.group if self.sharding.active and self.sharding.world > 1 else None
         self.sharding = WalkerSharding(group=False)            # nothing is exchanged inside a chain: every evaluation is local
         self.chain_rank = self.chain_group.rank if self.chain_group is not None else 0
         self.chain_world = self.chain_group.world if self.chain_group is not None else 1
-        if device_resident is None:
-            device_resident = getattr(likelihood, '_get_posterior_context', None) is not None and not len(getattr(likelihood, 'dependent_params', []))
-        self.device_resident = bool(device_resident)
+        self.device_resident = bool(self._device_default() if device_resident is None else device_resident)
         nlocal = len(self.local_chains())
         if vectorize is None: vectorize = max(1, min(64, 256 // max(nlocal, 1))) if self.device_resident else 1
         self.vectorize = int(vectorize)
@@ -371,11 +364,7 @@ class MCMCSampler(BasePosteriorSampler):
             burnin = self.learn_check['burnin'] = self.learn_check.get('burnin', burnin)
         self.learn_diagnostics = {}
         self._size_every = 0
-        if save_fn is not None:
-            if isinstance(save_fn, str): save_fn = [save_fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-            save_fn = list(save_fn)
-            if len(save_fn) != self.nchains or len(set(save_fn)) != self.nchains: raise ValueError('provide one file name per chain (or a template with *)')
-        self.save_fn = save_fn
+        self.save_fn = None if save_fn is None else _chain_file_names(save_fn, self.nchains, distinct=True)
         self._store = [None] * self.nchains          # per chain: [coords [n, ndim], logposterior [n], fweight [n]] so far, on every rank
         self._state = [None] * self.nchains          # per chain: (coords, logposterior, weight, naccepted)
         self._tries = 0
@@ -401,9 +390,7 @@ class MCMCSampler(BasePosteriorSampler):
             if matrix.shape != (ndim, ndim): raise ValueError('covariance must have shape ({0:d}, {0:d})'.format(ndim))
             given = (names, matrix)
         else:
-            from .io import ChainFile
-            sources = [source] if isinstance(source, str) or hasattr(source, 'arrays') else list(source)
-            files = [s if hasattr(s, 'arrays') else ChainFile.load(s) for s in sources]
+            files = _open_chain_files([source] if isinstance(source, str) or hasattr(source, 'arrays') else source)
             have = [name for name in names if all(name in f.arrays for f in files)]
             values, weights = [], []
             for f in files:
@@ -636,28 +623,22 @@ class MCMCSampler(BasePosteriorSampler):
         return bool(toret)
 
     # ---- checkpoints -----------------------------------------------------------------------------------------------------------------------------------------
-    def _chain_file(self, ichain):
-        from .io import ChainFile
+    def _chain_attrs(self, ichain):
         state = self._state[ichain]
-        attrs = {'sampler': self.name, 'tries': int(self._tries), 'counter_seed': int(self.counter_seed), 'vectorize': int(self.vectorize), 'chain_index': int(ichain),
-                 'state': {'coords': np.asarray(state[0]).tolist(), 'logposterior': None if state[1] is None else float(state[1]), 'weight': int(state[2]), 'naccepted': int(state[3])},
-                 'proposal_covariance': np.asarray(self.covariance).tolist()}
-        return ChainFile(dict(self.chains[ichain]), params={param.name: param for param in self.varied_params}, attrs=attrs)
+        return {'sampler': self.name, 'tries': int(self._tries), 'counter_seed': int(self.counter_seed), 'vectorize': int(self.vectorize), 'chain_index': int(ichain),
+                'state': {'coords': np.asarray(state[0]).tolist(), 'logposterior': None if state[1] is None else float(state[1]), 'weight': int(state[2]), 'naccepted': int(state[3])},
+                'proposal_covariance': np.asarray(self.covariance).tolist()}
 
     def save(self, fn=None):
         """Chains in the reference's checkpoint format (``Chain.save``); the attributes carry what continuing the very same chains needs (current state and weight,
         try counter, key of the counter-based draws, proposal covariance).  One file per chain; written by rank 0."""
-        if fn is None: fn = self.save_fn
-        if fn is None: raise ValueError('provide a file name')
-        if isinstance(fn, str): fn = [fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-        if len(fn) != self.nchains: raise ValueError('provide one file name per chain')
+        fn = self._save_names(fn)
         if self.chain_rank != 0: return
-        for ichain, name in enumerate(fn):
-            if self._store[ichain] is not None: self._chain_file(ichain).save(name)
+        chains = self.chains
+        self._write_chains((name, chains[ichain], self._chain_attrs(ichain)) for ichain, name in enumerate(fn) if self._store[ichain] is not None)
 
     def _load_one(self, ichain, source):
-        from .io import ChainFile
-        chain = source if hasattr(source, 'arrays') else ChainFile.load(source)
+        chain, = _open_chain_files([source])
         names = self.varied_params.names()
         coords = np.stack([np.asarray(chain.arrays[name], dtype='f8').ravel() for name in names], axis=-1)
         logp = np.asarray(chain.arrays['logposterior'], dtype='f8').ravel()

@@ -15,7 +15,7 @@ import numpy as np
 
 from .mclmc import _matvec
 from .nuts import _Draws
-from .samplers import BasePosteriorSampler, CounterRNG
+from .samplers import CounterRNG, _DeviceEngine, _EvidenceSampler, _HostEvidenceEngine, _expression, _open_chain_files, _run_chunks
 from .smc import factor, moments, next_scale, prefix_sums
 
 STREAM_PROPOSE, STREAM_ACCEPT, STREAM_SEED = 64, 65, 66
@@ -126,24 +126,16 @@ def _check_live(nlive):
         raise ValueError('nlive must be a multiple of 64 between 64 and {:d}, found {}'.format(MAX_LIVE, nlive))
 
 
-class _HostNested(object):
+class _HostNested(_HostEvidenceEngine):
     """NumPy statement of the device engine's stage machine (csrc/dl_nested.h, same records, same draws), around ``f(x [B, P]) -> (loglike [B], logprior [B])``."""
-    device_resident = False
+    _check_size, _counts, _nrecords = staticmethod(_check_live), 5, 5
 
     def __init__(self, f, nruns, nlive, n_params, widths, run_ids=None, seed=0, offset=0.):
-        self.f, self.K, self.N, self.P = f, int(nruns), int(nlive), int(n_params)
-        if not 1 <= self.P <= 64: raise ValueError('the sampler takes 1 .. 64 parameters, found {:d}'.format(self.P))
-        if self.K < 1: raise ValueError('nruns must be >= 1')
-        _check_live(self.N)
-        self.widths = np.asarray(widths, dtype='f8').reshape(self.P)
-        if not (np.all(self.widths > 0.) and np.all(np.isfinite(self.widths))): raise ValueError("the priors' widths must be positive and finite")
-        self.run_ids = np.arange(self.K) if run_ids is None else np.asarray(run_ids, dtype='i8')
-        self.offset, self.draws = float(offset), _NestedDraws(seed)
-        K, N, P = self.K, self.N, self.P
-        self.x, self.L, self.pi = np.zeros((K, N, P)), np.zeros((K, N)), np.zeros((K, N))
+        super(_HostNested, self).__init__(f, nruns, nlive, n_params, widths, run_ids, offset, 'run')
+        self.draws = _NestedDraws(seed)
+        K = self.K
         self.logx, self.logz, self.scale, self.iter, self.mode = np.zeros(K), np.full(K, -np.inf), np.ones(K), np.zeros(K, dtype='i8'), np.full(K, CLIMB, dtype='i4')
-        self.M, self.n_steps, self.iterations, self.evaluations, self._have_state = 0, 0, 0, 0, False
-        self.min_margin, self.ndecisions, self._decisions = np.inf, 0, None
+        self.M, self._have_state = 0, False
 
     # ---- set-up (dl_nested_set_hyper / set_live / set_state / get_state / get_decisions) ---------------------------------------------------------------------------
     def set_hyper(self, ndelete, n_steps, target_acceptance, dlogz, scale=1.):
@@ -155,11 +147,6 @@ class _HostNested(object):
         """(loglike, logprior) of rows x [B, P], -inf where there is no likelihood (not counted as evaluations of the runs)."""
         L, pi = self.f(np.ascontiguousarray(x))
         return np.array(L, dtype='f8'), np.array(pi, dtype='f8')
-
-    def _eval(self, x):
-        L, pi = self.f(np.ascontiguousarray(x.reshape(-1, self.P)))
-        self.evaluations += x.shape[0] * x.shape[1]
-        return np.array(L, dtype='f8').reshape(x.shape[:2]), np.array(pi, dtype='f8').reshape(x.shape[:2])
 
     @staticmethod
     def _check_terms(L, pi):
@@ -194,15 +181,7 @@ class _HostNested(object):
     def get_state(self):
         return tuple(a.copy() for a in (self.x, self.L, self.pi, self.logx, self.logz, self.iter, self.scale, self.mode))
 
-    def get_decisions(self):
-        return self._decisions
-
     # ---- an iteration -------------------------------------------------------------------------------------------------------------------------------------------
-    def _margin(self, margins):
-        if len(margins):
-            self.min_margin = min(self.min_margin, float(np.min(margins)))
-            self.ndecisions += len(margins)
-
     def _iteration(self, rec):
         hist, dcoords, dL, dpi, dlogw, count, modes, quota = rec
         K, N, P, M, n = self.K, self.N, self.P, self.M, self.n_steps
@@ -218,7 +197,7 @@ class _HostNested(object):
             logw, self.logx[k], self.logz[k] = evidence(self.L[k, dead], N, self.logx[k], self.logz[k])
             mean[k], cov[k] = survivor_moments(self.x[k], dead)
             chol[k] = factor(cov[k], self.widths)
-            r, margins = seed_ranks(self.draws.seed_uniform(self.iter[k], self.run_ids[k], M), N, M)
+            r, margins = seed_ranks(self.draws.seed_uniform(self.iter[k], self.ids[k], M), N, M)
             self._margin(margins)
             seeds[k] = order[k, r]
             slot = count[k]
@@ -228,12 +207,12 @@ class _HostNested(object):
         for j in range(n):
             prop = np.stack([self.x[k, order[k, :M]] for k in range(K)])          # [K, M, P]; the rows of a run that does not take part are evaluated and ignored
             for k in active:
-                z = self.draws.gauss(self.iter[k], j, self.run_ids[k], M, P)
+                z = self.draws.gauss(self.iter[k], j, self.ids[k], M, P)
                 prop[k] = prop[k] + (s[k] * (2.38 / np.sqrt(float(P)))) * _matvec(chol[k], z)
             Lp, pip = self._eval(prop)
             for k in active:
                 dead = order[k, :M]
-                logu = self.draws.log_uniform(self.iter[k], j, self.run_ids[k], M)
+                logu = self.draws.log_uniform(self.iter[k], j, self.ids[k], M)
                 with np.errstate(invalid='ignore'):
                     ok = (np.abs(Lp[k]) < np.inf) & (np.abs(pip[k]) < np.inf)
                     above = ok & (np.where(ok, Lp[k], 0.) > lstar[k])
@@ -268,28 +247,20 @@ class _HostNested(object):
         for _ in range(int(niterations)): self._iteration(tuple(buffers) + (int(quota),))
         self.iterations += int(niterations)
 
-    def counts(self, buffers):
-        return np.asarray(buffers[5])
-
     def modes(self, buffers):
         return np.asarray(buffers[6])
 
-    def records(self, buffers):
-        return tuple(np.asarray(b) for b in buffers[:5])
 
-
-class _DeviceNested(object):
-    """Runs resident on the GPU (``dl_nested_*``)."""
-    device_resident = True
+class _DeviceNested(_DeviceEngine):
+    """Runs resident on the GPU (``dl_nested_*``): the calls of :class:`_HostNested` go to the owner ``nested``."""
+    _counts, _nrecords, _counters = 5, 5, ('iterations', 'evaluations')
+    M = property(lambda self: self.nested.ndelete)
 
     def __init__(self, ctx, offset, nruns, nlive, widths, run_ids=None, seed=0):
         from ._lib import DeviceNested
         self.nested, self.ctx = DeviceNested(ctx, nruns, nlive, widths, run_ids=run_ids, seed=seed, offset=offset), ctx
+        self._owner = self.nested
         self.K, self.N, self.P, self.offset = int(nruns), int(nlive), self.nested.n_params, float(offset)
-
-    def set_hyper(self, ndelete, n_steps, target_acceptance, dlogz, scale=1.):
-        self.nested.set_hyper(ndelete, n_steps, target_acceptance, dlogz, scale)
-        self.M = int(ndelete)
 
     def terms(self, x):
         """(loglike, logprior) of rows x [B, P] through the context's dl_eval_batch, -inf where the status is not 0."""
@@ -303,57 +274,18 @@ class _DeviceNested(object):
         L[status != 0] = -np.inf
         return L, pi
 
-    def set_live(self, coords):
-        self.nested.set_live(coords)
-
-    def set_state(self, *state):
-        self.nested.set_state(*state)
-
-    def get_state(self):
-        return self.nested.get_state()
-
-    def get_decisions(self):
-        return self.nested.get_decisions()
-
-    def buffers(self, quota):
-        return self.nested.buffers(quota)
-
-    def run(self, niterations, quota, buffers):
-        self.nested.run(niterations, quota, buffers)
-
-    def counts(self, buffers):
-        return buffers[5].cpu().numpy()
-
     def modes(self, buffers):
-        return buffers[6].cpu().numpy()        # the one synchronisation of a chunk
-
-    def records(self, buffers):
-        return tuple(b.cpu().numpy() for b in buffers[:5])
-
-    @property
-    def iterations(self):
-        return self.nested.info('iterations')
-
-    @property
-    def evaluations(self):
-        return self.nested.info('evaluations')
+        return buffers[6].cpu().numpy()        # the one synchronisation of a chunk (the counts are read after the last)
 
 
 def run_batch(engine, niterations, chunk=None):
     """At most ``niterations`` iterations of every run in chunks of at most ``chunk``, ending early once every run is at rest (the modes are read once per chunk):
     (history [K, n, 6], dead coords [K, n, M, P], dead loglike, logprior, logweight [K, n, M], counts [K], modes [K]); rows beyond counts[k] are not written."""
-    niterations = int(niterations)
-    buffers = engine.buffers(max(niterations, 1))
-    left = niterations
-    while left > 0:
-        step = left if chunk is None else min(int(chunk), left)
-        engine.run(step, niterations, buffers)
-        left -= step
-        if not np.any(engine.modes(buffers) != REST): break
+    buffers = _run_chunks(engine, niterations, chunk, stop=lambda buffers: not np.any(engine.modes(buffers) != REST))
     return engine.records(buffers) + (engine.counts(buffers).copy(), engine.modes(buffers).copy())
 
 
-class NestedSampler(BasePosteriorSampler):
+class NestedSampler(_EvidenceSampler):
     """``NestedSampler(likelihood, nlive=1024, chains=1, ndelete='nlive // 4', n_steps='4 * ndim', target_acceptance=0.234, dlogz=0.01, seed=None, save_fn=None,
     device_resident=None)``: nested sampling from the PRIOR to the posterior, with the Bayesian evidence and its error from a single run.
 
@@ -372,63 +304,23 @@ class NestedSampler(BasePosteriorSampler):
     ``information`` [chains] (H), ``logz_mean`` = log of the mean Z, ``logz_std`` (the scatter of ``logz``; ``None`` for one run), ``history`` (dict of [chains, T]
     arrays, NaN beyond a run's last iteration), ``nevaluations``, ``chains`` (per run name -> [n] with ``logposterior``, ``loglikelihood``, ``logweight`` and ``aweight``:
     the dead points in the order of their death, then the closing live points), :meth:`samples`."""
-    name = 'nested'
+    name, _words = 'nested', ('NestedSampler', 'live points', 'run')
 
     def __init__(self, likelihood, nlive=1024, chains=1, ndelete='nlive // 4', n_steps='4 * ndim', target_acceptance=0.234, dlogz=0.01, seed=None, save_fn=None,
                  device_resident=None, **kwargs):
         super(NestedSampler, self).__init__(likelihood, seed=seed, **kwargs)
-        if self.sharding.active and self.sharding.world > 1:
-            raise NotImplementedError('NestedSampler keeps all live points of a run on one GPU: run one sampler per rank (different seeds) and pool their logz')
-        ndim = len(self.varied_params)
-        if not 1 <= ndim <= 64: raise ValueError('NestedSampler takes 1 .. 64 varied parameters, found {:d}'.format(ndim))
-        resume = None
-        if not isinstance(chains, (int, np.integer)):
-            resume = [chains] if isinstance(chains, (str, dict)) or hasattr(chains, 'arrays') else list(chains)
-            chains = len(resume)
-        self.nchains, self.nlive = int(chains), int(nlive)
-        if self.nchains < 1: raise ValueError('chains must be >= 1')
+        resume = self._setup(chains, seed, save_fn, device_resident)
+        ndim, self.nlive, self._offset = len(self.varied_params), int(nlive), 0.
         _check_live(self.nlive)
-        if isinstance(ndelete, str): ndelete = int(eval(ndelete, {'nlive': self.nlive}))
-        if isinstance(n_steps, str): n_steps = int(eval(n_steps, {'ndim': ndim}))
-        self.ndelete, self.n_steps, self.target_acceptance, self.dlogz = int(ndelete), int(n_steps), float(target_acceptance), float(dlogz)
+        self.ndelete, self.n_steps = int(_expression(ndelete, nlive=self.nlive)), int(_expression(n_steps, ndim=ndim))
+        self.target_acceptance, self.dlogz = float(target_acceptance), float(dlogz)
         _check_hyper(self.nlive, self.ndelete, self.n_steps, self.target_acceptance, self.dlogz, 1.)
-        for param in self.varied_params:
-            if not param.prior.is_proper():
-                raise ValueError('NestedSampler draws its live points from the priors: the prior of {} is not proper'.format(param.name))
-        self.widths = np.array([param.prior.limits[1] - param.prior.limits[0] if param.prior.dist == 'uniform' else param.prior.std() for param in self.varied_params], dtype='f8')
-        if device_resident is None:
-            device_resident = getattr(likelihood, '_get_posterior_context', None) is not None and not len(getattr(likelihood, 'dependent_params', []))
-        self.device_resident = bool(device_resident)
-        if seed is None: seed = int(self.rng.randint(0, 2**32, dtype=np.uint64))
-        self.counter_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        if save_fn is not None:
-            if isinstance(save_fn, str): save_fn = [save_fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-            save_fn = list(save_fn)
-            if len(save_fn) != self.nchains or len(set(save_fn)) != self.nchains: raise ValueError('provide one file name per chain (or a template with *)')
-        self.save_fn = save_fn
-        self._engine, self._state, self._offset = None, None, 0.
         self._history = [np.zeros((0, 6)) for _ in range(self.nchains)]
         self._dead = [[np.zeros((0, ndim)), np.zeros(0), np.zeros(0), np.zeros(0)] for _ in range(self.nchains)]       # coords, loglike, logprior, logweight
         self.prior_fraction = np.ones(self.nchains)
-        self._evaluations = 0
         if resume is not None: self._resume(resume)
 
     # ---- engine -------------------------------------------------------------------------------------------------------------------------------------------------
-    def _host_terms(self, values):
-        """(loglike, logprior) of rows through the likelihood's own call surface (likelihoods without a device context)."""
-        from .parameter import Samples
-        values = np.atleast_2d(values)
-        logprior = self.logprior(values)
-        loglike = np.full(values.shape[0], -np.inf)
-        finite = np.isfinite(logprior) & ~np.isnan(values).any(axis=1)
-        if finite.any():
-            (_, derived), errors = self._vlikelihood(Samples(values[finite].T, params=self.varied_params).to_dict())
-            column = np.array(derived[self.likelihood._param_loglikelihood], dtype='f8')
-            column[np.isnan(column)] = -np.inf
-            for ipoint in errors: column[ipoint] = -np.inf
-            loglike[finite] = column
-        return loglike, logprior
-
     def _draw(self, size):
         return np.column_stack([param.prior.sample(size=size, random_state=self.rng) for param in self.varied_params])
 
@@ -552,38 +444,17 @@ class NestedSampler(BasePosteriorSampler):
         if closed is None: return np.full(self.nchains, np.nan)
         return np.array([c['information'] for c in closed])
 
-    @property
-    def logz_mean(self):
-        logz = self.logz
-        top = logz.max()
-        return float(top + np.log(np.mean(np.exp(logz - top))))
-
-    @property
-    def logz_std(self):
-        return float(np.std(self.logz, ddof=1)) if self.nchains > 1 else None
-
-    @property
-    def nevaluations(self):
-        return int(self._evaluations)
-
     def save(self, fn=None):
         """One file per run in the reference's checkpoint format; attributes ``{'sampler': 'nested', 'seed', 'state', 'history', ...}``: the state continues the run."""
-        from .io import ChainFile
-        if fn is None: fn = self.save_fn
-        if fn is None: raise ValueError('provide a file name')
-        if isinstance(fn, str): fn = [fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-        if len(fn) != self.nchains: raise ValueError('provide one file name per chain')
+        fn = self._save_names(fn)
         if self._state is None: return
-        for k, (chain, name) in enumerate(zip(self.chains, fn)):
-            attrs = {'sampler': self.name, 'seed': self.counter_seed, 'run': k, 'state': [np.asarray(a[k]) for a in self._state], 'history': self._history[k],
-                     'hyper': [self.ndelete, self.n_steps, self.target_acceptance, self.dlogz], 'evaluations': self._evaluations, 'offset': self._offset,
-                     'prior_fraction': float(self.prior_fraction[k])}
-            ChainFile(dict(chain), params={param.name: param for param in self.varied_params}, attrs=attrs).save(name)
+        self._write_chains((name, chain, {'sampler': self.name, 'seed': self.counter_seed, 'run': k, 'state': [np.asarray(a[k]) for a in self._state], 'history': self._history[k],
+                                          'hyper': [self.ndelete, self.n_steps, self.target_acceptance, self.dlogz], 'evaluations': self._evaluations,
+                                          'offset': self._offset, 'prior_fraction': float(self.prior_fraction[k])}) for k, (chain, name) in enumerate(zip(self.chains, fn)))
 
     def _resume(self, sources):
         """Continue the runs saved by :meth:`save`: live points, volumes, evidences, counters, scales, modes (and the dead points so far)."""
-        from .io import ChainFile
-        files = [s if hasattr(s, 'arrays') else ChainFile.load(s) for s in sources]
+        files = _open_chain_files(sources)
         names = self.varied_params.names()
         for f in files:
             if f.attrs.get('sampler', None) != self.name or 'state' not in f.attrs: raise ValueError('not a chain file of NestedSampler')

@@ -13,7 +13,7 @@ Warm-up as :class:`~desilike_amd.hmc.HMCSampler`: per-chain dual averaging of th
 regularisation), dual averaging restarted, final step size exp(mean over chains of log eps-bar)."""
 import numpy as np
 
-from .samplers import BasePosteriorSampler, CounterRNG, _batch_iterate
+from .samplers import BasePosteriorSampler, CounterRNG, _DeviceEngine, _batch_iterate, _open_chain_files, _parse_chains
 from .parallel import WalkerSharding
 
 STREAM_MOMENTUM, STREAM_DIRECTION, STREAM_SELECT = 32, 33, 34
@@ -280,43 +280,15 @@ class _HostNUTS(object):
         return tuple(np.asarray(b) for b in buffers[:3])
 
 
-class _DeviceNUTS(object):
-    """Chains of this rank resident on the GPU (``dl_nuts_*``)."""
-    device_resident = True
+class _DeviceNUTS(_DeviceEngine):
+    """Chains of this rank resident on the GPU (``dl_nuts_*``): the calls of :class:`_HostNUTS` go to the owner ``nuts``."""
+    _counters = ('steps',)
 
     def __init__(self, ctx, offset, chain_ids, max_num_doublings, divergence_threshold, seed, gradient, fd_delta, fd_limits):
         from ._lib import DeviceNUTS
-        self.nuts = DeviceNUTS(ctx, len(chain_ids), chain_ids=chain_ids, max_num_doublings=max_num_doublings, divergence_threshold=divergence_threshold, seed=seed,
-                               offset=offset, gradient=gradient, fd_delta=fd_delta, fd_limits=fd_limits)
+        self.nuts = self._owner = DeviceNUTS(ctx, len(chain_ids), chain_ids=chain_ids, max_num_doublings=max_num_doublings, divergence_threshold=divergence_threshold,
+                                             seed=seed, offset=offset, gradient=gradient, fd_delta=fd_delta, fd_limits=fd_limits)
         self.C, self.P = len(chain_ids), self.nuts.n_params
-
-    def set_mass(self, inverse_mass, step_size):
-        self.nuts.set_mass(inverse_mass, step_size)
-
-    def set_state(self, coords, logposterior=None, iterations=None):
-        self.nuts.set_state(coords, logposterior=logposterior, iterations=iterations)
-
-    def get_state(self):
-        return self.nuts.get_state()
-
-    def set_adaptation(self, enabled, target_acceptance=0.8, initial_step_size=1.):
-        self.nuts.set_adaptation(enabled, target_acceptance=target_acceptance, initial_step_size=initial_step_size)
-
-    def buffers(self, quota):
-        return self.nuts.buffers(quota)
-
-    def run(self, nsteps, quota, buffers, thin_by=1):
-        self.nuts.run(nsteps, quota, buffers, thin_by=thin_by)
-
-    def counts(self, buffers):
-        return buffers[3].cpu().numpy()        # the one synchronisation of a chunk
-
-    def records(self, buffers):
-        return tuple(b.cpu().numpy() for b in buffers[:3])
-
-    @property
-    def steps(self):
-        return self.nuts.info('steps')
 
 
 def run_batch(engine, quota, thin_by=1, chunk=32):
@@ -345,13 +317,8 @@ class NUTSSampler(BasePosteriorSampler):
                  gradient='auto', seed=None, save_fn=None, device_resident=None, chunk=32, **kwargs):
         if integrator != 'velocity_verlet':
             raise NotImplementedError('integrator {!r} is not built: NUTSSampler integrates with velocity_verlet only'.format(integrator))
-        resume = None
-        if not isinstance(chains, (int, np.integer)):
-            resume = [chains] if isinstance(chains, str) or hasattr(chains, 'arrays') else list(chains)
-            chains = len(resume)
+        self.nchains, resume = _parse_chains(chains)
         super(NUTSSampler, self).__init__(likelihood, seed=seed, **kwargs)
-        self.nchains = int(chains)
-        if self.nchains < 1: raise ValueError('chains must be >= 1')
         self.step_size, self.max_num_doublings, self.divergence_threshold = float(step_size), int(max_num_doublings), float(divergence_threshold)
         if not self.step_size > 0.: raise ValueError('step_size must be positive')
         if not 1 <= self.max_num_doublings <= 15: raise ValueError('max_num_doublings must be in [1, 15]')
@@ -362,11 +329,8 @@ class NUTSSampler(BasePosteriorSampler):
         self.sharding = WalkerSharding(group=False)
         self.chain_rank = self.chain_group.rank if self.chain_group is not None else 0
         self.chain_world = self.chain_group.world if self.chain_group is not None else 1
-        if device_resident is None:
-            device_resident = getattr(likelihood, '_get_posterior_context', None) is not None and not len(getattr(likelihood, 'dependent_params', []))
-        self.device_resident = bool(device_resident)
-        if seed is None: seed = int(self.rng.randint(0, 2**32, dtype=np.uint64))
-        self.counter_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.device_resident = bool(self._device_default() if device_resident is None else device_resident)
+        self.counter_seed = self._counter_seed(seed)
         if adaptation is True: adaptation = {}
         self.adaptation = None if adaptation is False or adaptation is None else dict(adaptation)
         from .hmc import HMCSampler
@@ -558,21 +522,15 @@ class NUTSSampler(BasePosteriorSampler):
 
     def save(self, fn=None):
         """One file per chain in the reference's checkpoint format; attributes ``{'sampler': 'nuts', 'hyp': ...}`` and the chain's iteration counter ('iteration')."""
-        from .io import ChainFile
-        if fn is None: fn = self.save_fn
-        if fn is None: raise ValueError('provide a file name')
-        if isinstance(fn, str): fn = [fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-        if len(fn) != self.nchains: raise ValueError('provide one file name per chain')
+        fn = self._save_names(fn)
         if self.chain_rank != 0 or self._store is None: return
         hyp = None if self.hyp is None else {'step_size': self.hyp['step_size'], 'inverse_mass_matrix': np.asarray(self.hyp['inverse_mass_matrix']).tolist()}
-        for c, (chain, name) in enumerate(zip(self.chains, fn)):
-            attrs = {'sampler': self.name, 'hyp': hyp, 'iteration': int(self._state[2][c]), 'seed': self.counter_seed}
-            ChainFile(dict(chain), params={param.name: param for param in self.varied_params}, attrs=attrs).save(name)
+        self._write_chains((name, chain, {'sampler': self.name, 'hyp': hyp, 'iteration': int(self._state[2][c]), 'seed': self.counter_seed})
+                           for c, (chain, name) in enumerate(zip(self.chains, fn)))
 
     def _resume(self, sources):
         """Continue the chains saved by :meth:`save`: last points, iteration counters, hyper-parameters (no new warm-up)."""
-        from .io import ChainFile
-        files = [s if hasattr(s, 'arrays') else ChainFile.load(s) for s in sources]
+        files = _open_chain_files(sources)
         names = self.varied_params.names()
         points = np.array([[np.asarray(f.arrays[name], dtype='f8').ravel()[-1] for name in names] for f in files])
         logp = np.array([np.asarray(f.arrays['logposterior'], dtype='f8').ravel()[-1] for f in files])

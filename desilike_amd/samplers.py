@@ -105,6 +105,53 @@ def _sync_random_state(rng, seed, sharding):
     return rng, seed
 
 
+def _parse_chains(chains):
+    """``chains``: a number of chains, or what to resume them from -- ONE source (a file name, a dict, an object with ``.arrays``) or a sequence of sources, one per
+    chain.  Returns ``(nchains, sources or None)``."""
+    if isinstance(chains, (int, np.integer)):
+        nchains, resume = int(chains), None
+    else:
+        resume = [chains] if isinstance(chains, (str, dict)) or hasattr(chains, 'arrays') else list(chains)
+        nchains = len(resume)
+    if nchains < 1: raise ValueError('chains must be >= 1')
+    return nchains, resume
+
+
+def _chain_file_names(fn, nchains, distinct=False):
+    """One file name per chain from ``fn``: a name (of a single chain), a template with ``*`` (replaced by the chain's index) or a list; ``distinct``: two chains must
+    not share a file (what a constructor asks of ``save_fn``)."""
+    if isinstance(fn, str): fn = [fn.replace('*', str(ichain)) for ichain in range(nchains)]
+    fn = list(fn)
+    if len(fn) != nchains or (distinct and len(set(fn)) != nchains):
+        raise ValueError('provide one file name per chain' + (' (or a template with *)' if distinct else ''))
+    return fn
+
+
+def _open_chain_files(sources):
+    """The sources of a resume as :class:`~desilike_amd.io.ChainFile` (file names are loaded)."""
+    from .io import ChainFile
+    return [source if hasattr(source, 'arrays') else ChainFile.load(source) for source in sources]
+
+
+def _expression(value, **names):
+    """A number, or an expression of ``names`` (as ``n_steps='2 * ndim'``)."""
+    return int(eval(value, dict(names))) if isinstance(value, str) else value
+
+
+def _run_chunks(engine, niterations, chunk=None, stop=None):
+    """``niterations`` iterations of an evidence engine into fresh record buffers, in chunks of at most ``chunk``, ending early once ``stop(buffers)`` (asked once per
+    chunk) holds.  Returns the buffers."""
+    niterations = int(niterations)
+    buffers = engine.buffers(max(niterations, 1))
+    left = niterations
+    while left > 0:
+        step = left if chunk is None else min(int(chunk), left)
+        engine.run(step, niterations, buffers)
+        left -= step
+        if stop is not None and stop(buffers): break
+    return buffers
+
+
 class BasePosteriorSampler(object):
 
     def __init__(self, likelihood, rng=None, seed=None, max_tries=1000, ref_scale=1., sharding=None):
@@ -197,6 +244,140 @@ class BasePosteriorSampler(object):
         if not np.isfinite(logposterior).all():
             raise ValueError('Could not find finite log posterior after {:d} tries'.format(self.max_tries))
         return start, logposterior
+
+    # ---- what the samplers with chains share ----------------------------------------------------------------------------------------------------------------------
+    def _device_default(self):
+        """Default of ``device_resident``: where the likelihood has a device context and no parameter derived by an expression (those are computed by the host wrapper
+        of the context: a device-resident sampler does not see them)."""
+        return getattr(self.likelihood, '_get_posterior_context', None) is not None and not len(getattr(self.likelihood, 'dependent_params', []))
+
+    def _counter_seed(self, seed):
+        """64-bit key of the counter-based draws: ``seed``, or 32 bits from the (rank-synchronised) host generator."""
+        if seed is None: seed = int(self.rng.randint(0, 2**32, dtype=np.uint64))
+        return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+    def _save_names(self, fn=None):
+        """The file of every chain for :meth:`save`: from ``fn`` (default ``save_fn``)."""
+        if fn is None: fn = self.save_fn
+        if fn is None: raise ValueError('provide a file name')
+        return _chain_file_names(fn, self.nchains)
+
+    def _write_chains(self, files):
+        """``files``: (file name, chain, attrs) of every chain to write, in the reference's checkpoint format (``Chain.save``, parameter.py:2164-2182)."""
+        from .io import ChainFile
+        params = {param.name: param for param in self.varied_params}
+        for name, chain, attrs in files:
+            ChainFile(dict(chain), params=params, attrs=attrs).save(name)
+
+
+class _DeviceEngine(object):
+    """What the device engines of NUTS, MCLMC, SMC and nested sampling share.  A subclass builds the ``_lib`` owner (``self._owner``, also under the sampler's name) and
+    states its sizes; every call it does not define itself (``set_*``, ``get_*``, ``buffers``, ``run`` ...) goes to the owner, whose methods have the signatures of the host
+    engine's, and the names in ``_counters`` are read from the owner's ``info``.  ``_counts``: the buffer that holds the record counts; ``_nrecords``: the leading
+    buffers that are the records."""
+    device_resident = True
+    _counts, _nrecords, _counters = 3, 3, ()
+
+    def __getattr__(self, name):
+        if name.startswith('_'): raise AttributeError(name)      # (no owner yet)
+        if name in self._counters: return self._owner.info(name)
+        return getattr(self._owner, name)
+
+    def counts(self, buffers):
+        return buffers[self._counts].cpu().numpy()        # the one synchronisation of a chunk
+
+    def records(self, buffers):
+        return tuple(b.cpu().numpy() for b in buffers[:self._nrecords])
+
+
+class _HostEvidenceEngine(object):
+    """What the NumPy statements of the two evidence engines share (:class:`~desilike_amd.smc._HostSMC`, :class:`~desilike_amd.nested._HostNested`): ``K`` populations of
+    ``N`` points in ``P`` parameters around ``f(x [B, P]) -> (loglike [B], logprior [B])``, the count of evaluations, and the smallest margin of the discrete decisions."""
+    device_resident = False
+    _counts, _nrecords = 3, 3
+
+    def __init__(self, f, K, N, P, widths, ids, offset, unit):
+        self.f, self.K, self.N, self.P = f, int(K), int(N), int(P)
+        if not 1 <= self.P <= 64: raise ValueError('the sampler takes 1 .. 64 parameters, found {:d}'.format(self.P))
+        if self.K < 1: raise ValueError('n{}s must be >= 1'.format(unit))
+        self._check_size(self.N)
+        self.widths = np.asarray(widths, dtype='f8').reshape(self.P)
+        if not (np.all(self.widths > 0.) and np.all(np.isfinite(self.widths))): raise ValueError("the priors' widths must be positive and finite")
+        self.ids, self.offset = np.arange(self.K) if ids is None else np.asarray(ids, dtype='i8'), float(offset)
+        self.x, self.L, self.pi = np.zeros((self.K, self.N, self.P)), np.zeros((self.K, self.N)), np.zeros((self.K, self.N))
+        self.n_steps, self.iterations, self.evaluations = 0, 0, 0
+        self.min_margin, self.ndecisions, self._decisions = np.inf, 0, None
+
+    def _eval(self, x):
+        L, pi = self.f(np.ascontiguousarray(x.reshape(-1, self.P)))
+        self.evaluations += x.shape[0] * x.shape[1]
+        return np.array(L, dtype='f8').reshape(x.shape[:2]), np.array(pi, dtype='f8').reshape(x.shape[:2])
+
+    def _margin(self, margins):
+        if len(margins):
+            self.min_margin = min(self.min_margin, float(np.min(margins)))
+            self.ndecisions += len(margins)
+
+    def get_decisions(self):
+        return self._decisions
+
+    def counts(self, buffers):
+        return np.asarray(buffers[self._counts])
+
+    def records(self, buffers):
+        return tuple(np.asarray(b) for b in buffers[:self._nrecords])
+
+
+class _EvidenceSampler(BasePosteriorSampler):
+    """What :class:`~desilike_amd.smc.SMCSampler` and :class:`~desilike_amd.nested.NestedSampler` share: populations that start from PROPER priors and stay on one GPU,
+    ``chains`` independent populations whose scatter is the error of ``logz``.  ``_words``: (the sampler, its points, one population) in the messages."""
+    _words = None
+
+    def _setup(self, chains, seed, save_fn, device_resident):
+        """The part of the constructor after ``BasePosteriorSampler.__init__``; returns the sources to resume from (or ``None``)."""
+        title, points, unit = self._words
+        if self.sharding.active and self.sharding.world > 1:
+            raise NotImplementedError('{} keeps all {} of a {} on one GPU: run one sampler per rank (different seeds) and pool their logz'.format(title, points, unit))
+        ndim = len(self.varied_params)
+        if not 1 <= ndim <= 64: raise ValueError('{} takes 1 .. 64 varied parameters, found {:d}'.format(title, ndim))
+        self.nchains, resume = _parse_chains(chains)
+        for param in self.varied_params:
+            if not param.prior.is_proper():
+                raise ValueError('{} draws its {} from the priors: the prior of {} is not proper'.format(title, points, param.name))
+        self.widths = np.array([param.prior.limits[1] - param.prior.limits[0] if param.prior.dist == 'uniform' else param.prior.std() for param in self.varied_params], dtype='f8')
+        self.device_resident = bool(self._device_default() if device_resident is None else device_resident)
+        self.counter_seed = self._counter_seed(seed)
+        self.save_fn = None if save_fn is None else _chain_file_names(save_fn, self.nchains, distinct=True)
+        self._engine, self._state, self._evaluations = None, None, 0
+        return resume
+
+    def _host_terms(self, values):
+        """(loglike, logprior) of rows through the likelihood's own call surface (likelihoods without a device context)."""
+        values = np.atleast_2d(values)
+        logprior = self.logprior(values)
+        loglike = np.full(values.shape[0], -np.inf)
+        finite = np.isfinite(logprior) & ~np.isnan(values).any(axis=1)
+        if finite.any():
+            (_, derived), errors = self._vlikelihood(Samples(values[finite].T, params=self.varied_params).to_dict())
+            column = np.array(derived[self.likelihood._param_loglikelihood], dtype='f8')
+            column[np.isnan(column)] = -np.inf
+            for ipoint in errors: column[ipoint] = -np.inf
+            loglike[finite] = column
+        return loglike, logprior
+
+    @property
+    def logz_mean(self):
+        logz = self.logz
+        top = logz.max()
+        return float(top + np.log(np.mean(np.exp(logz - top))))
+
+    @property
+    def logz_std(self):
+        return float(np.std(self.logz, ddof=1)) if self.nchains > 1 else None
+
+    @property
+    def nevaluations(self):
+        return int(self._evaluations)
 
 
 class EnsembleStretchMove(object):
@@ -452,16 +633,9 @@ class EmceeSampler(BasePosteriorSampler):
         ndim = len(self.varied_params)
         if nwalkers is None:
             nwalkers = 2 * max((int(2.5 * ndim) + 1) // 2, 2)                            # samplers/emcee.py:66
-        if isinstance(nwalkers, str):
-            nwalkers = int(eval(nwalkers, {'ndim': ndim}))
-        self.nwalkers = int(nwalkers)
+        self.nwalkers = int(_expression(nwalkers, ndim=ndim))
         self.a = float(a)
-        resume = None
-        if not isinstance(chains, (int, np.integer)):
-            resume = [chains] if isinstance(chains, (str, dict)) or hasattr(chains, 'arrays') else list(chains)
-            chains = len(resume)
-        self.nchains = int(chains)
-        if self.nchains < 1: raise ValueError('chains must be >= 1')
+        self.nchains, resume = _parse_chains(chains)
         self.chain_parallel = self.nchains > 1
         self.chain_group = None
         if self.chain_parallel:
@@ -470,10 +644,7 @@ class EmceeSampler(BasePosteriorSampler):
             self.sharding = WalkerSharding(group=False)
         self.chain_rank = self.chain_group.rank if self.chain_group is not None else 0
         self.chain_world = self.chain_group.world if self.chain_group is not None else 1
-        if device_resident is None:
-            # (parameters derived by an expression are computed by the host wrapper of the context: the device-resident ensemble does not see them)
-            device_resident = use_emcee is not True and getattr(likelihood, '_get_posterior_context', None) is not None and not len(getattr(likelihood, 'dependent_params', []))
-        self.device_resident = bool(device_resident)
+        self.device_resident = bool(use_emcee is not True and self._device_default() if device_resident is None else device_resident)
         emcee = None
         if use_emcee is not False and not self.device_resident and not self.chain_parallel and counter_seeds is None:
             try:
@@ -488,13 +659,7 @@ class EmceeSampler(BasePosteriorSampler):
         self.counter_seeds = None if counter_seeds is None else [int(key) & 0xFFFFFFFFFFFFFFFF for key in np.atleast_1d(counter_seeds)]
         if self.counter_seeds is not None and len(self.counter_seeds) != self.nchains:
             raise ValueError('provide one counter seed per chain')
-        if save_fn is not None:
-            if isinstance(save_fn, str):
-                save_fn = [save_fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-            save_fn = list(save_fn)
-            if len(save_fn) != self.nchains or len(set(save_fn)) != self.nchains:
-                raise ValueError('provide one file name per chain (or a template with *)')
-        self.save_fn = save_fn
+        self.save_fn = None if save_fn is None else _chain_file_names(save_fn, self.nchains, distinct=True)
         self._blocks = [_ChainStore() for _ in range(self.nchains)]   # per chain: coords [n, nwalkers, ndim], logposterior [n, nwalkers] so far, on every rank
         self._state = [None] * self.nchains           # per chain: (coords [nwalkers, ndim], logposterior [nwalkers]) after the last update
         self._iterations = [0] * self.nchains         # updates done (the counter of the chain's generator)
@@ -734,27 +899,21 @@ class EmceeSampler(BasePosteriorSampler):
         return out[0] if self.nchains == 1 else out
 
     # ---- checkpoints -----------------------------------------------------------------------------------------------------------------------------------------
-    def _chain_file(self, ichain):
-        from .io import ChainFile
-        attrs = {'sampler': self.name, 'nwalkers': self.nwalkers, 'a': self.a, 'iteration': int(self._iterations[ichain]), 'naccepted': np.asarray(self._accepted[ichain]).tolist(),
-                 'counter_seed': None if self.counter_seeds is None else int(self.counter_seeds[ichain])}
-        return ChainFile(dict(self.chains[ichain]), params={param.name: param for param in self.varied_params}, attrs=attrs)
+    def _chain_attrs(self, ichain):
+        return {'sampler': self.name, 'nwalkers': self.nwalkers, 'a': self.a, 'iteration': int(self._iterations[ichain]), 'naccepted': np.asarray(self._accepted[ichain]).tolist(),
+                'counter_seed': None if self.counter_seeds is None else int(self.counter_seeds[ichain])}
 
     def save(self, fn=None):
         """Chains in the reference's checkpoint format (``Chain.save``, parameter.py:2164-2182: read by the reference's ``Chain.load`` and by :meth:`load`); the
         attributes carry what resuming the very same chain needs (iteration counter and key of the counter-based generator, accepted counts).  One file per chain
         (``fn``: a name for a single chain, a list, or a template with ``*``; default ``save_fn``); written by rank 0 of the chains' group."""
-        if fn is None: fn = self.save_fn
-        if fn is None: raise ValueError('provide a file name')
-        if isinstance(fn, str): fn = [fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-        if len(fn) != self.nchains: raise ValueError('provide one file name per chain')
+        fn = self._save_names(fn)
         if self.chain_rank != 0 or (not self.chain_parallel and self.sharding.rank != 0): return
-        for ichain, name in enumerate(fn):
-            if self._blocks[ichain]: self._chain_file(ichain).save(name)
+        chains = self.chains
+        self._write_chains((name, chains[ichain], self._chain_attrs(ichain)) for ichain, name in enumerate(fn) if self._blocks[ichain])
 
     def _load_one(self, ichain, source):
-        from .io import ChainFile
-        chain = source if hasattr(source, 'arrays') else ChainFile.load(source)
+        chain, = _open_chain_files([source])
         names = self.varied_params.names()
         coords = np.stack([np.asarray(chain.arrays[name], dtype='f8') for name in names], axis=-1)
         logp = np.asarray(chain.arrays['logposterior'], dtype='f8')
@@ -776,9 +935,7 @@ class EmceeSampler(BasePosteriorSampler):
     def load(self, fn):
         """Resume from files written by :meth:`save` (one name, a list, or a template with ``*``): the next :meth:`run` continues these chains -- positions,
         log-posteriors, generator key and counter are handed to new ensembles, so the continuation is the chain an uninterrupted run would give."""
-        if isinstance(fn, str): fn = [fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-        if len(fn) != self.nchains: raise ValueError('provide one file name per chain')
-        for ichain, name in enumerate(fn):
+        for ichain, name in enumerate(_chain_file_names(fn, self.nchains)):
             self._load_one(ichain, name)
         if self.counter_seeds is not None and any(key is None for key in self.counter_seeds):
             self.counter_seeds = None    # (files without keys, e.g. written by the reference: new keys are drawn)

@@ -15,7 +15,7 @@ import numpy as np
 
 from .mclmc import _matvec
 from .nuts import _Draws
-from .samplers import BasePosteriorSampler, CounterRNG
+from .samplers import CounterRNG, _DeviceEngine, _EvidenceSampler, _HostEvidenceEngine, _expression, _open_chain_files, _run_chunks
 
 STREAM_PROPOSE, STREAM_ACCEPT, STREAM_RESAMPLE = 50, 51, 52
 HISTORY_FIELDS = ('beta', 'logz', 'ess', 'acceptance', 'scale')
@@ -153,35 +153,21 @@ def _check_particles(nparticles):
         raise ValueError('nparticles must be a multiple of 64 between 64 and {:d}, found {}'.format(MAX_PARTICLES, nparticles))
 
 
-class _HostSMC(object):
+class _HostSMC(_HostEvidenceEngine):
     """NumPy statement of the device engine's stage machine (csrc/dl_smc.h, same records, same draws), around ``f(x [B, P]) -> (loglike [B], logprior [B])``."""
-    device_resident = False
+    _check_size = staticmethod(_check_particles)
 
     def __init__(self, f, nsystems, nparticles, n_params, widths, system_ids=None, seed=0, offset=0.):
-        self.f, self.K, self.N, self.P = f, int(nsystems), int(nparticles), int(n_params)
-        if not 1 <= self.P <= 64: raise ValueError('the sampler takes 1 .. 64 parameters, found {:d}'.format(self.P))
-        if self.K < 1: raise ValueError('nsystems must be >= 1')
-        _check_particles(self.N)
-        self.widths = np.asarray(widths, dtype='f8').reshape(self.P)
-        if not (np.all(self.widths > 0.) and np.all(np.isfinite(self.widths))): raise ValueError("the priors' widths must be positive and finite")
-        self.system_ids = np.arange(self.K) if system_ids is None else np.asarray(system_ids, dtype='i8')
-        self.offset, self.draws = float(offset), _SmcDraws(seed)
-        K, N, P = self.K, self.N, self.P
-        self.x, self.L, self.pi = np.zeros((K, N, P)), np.zeros((K, N)), np.zeros((K, N))
+        super(_HostSMC, self).__init__(f, nsystems, nparticles, n_params, widths, system_ids, offset, 'system')
+        self.draws = _SmcDraws(seed)
+        K, P = self.K, self.P
         self.beta, self.logz, self.scale, self.iter, self.chol = np.zeros(K), np.zeros(K), np.ones(K), np.zeros(K, dtype='i8'), np.zeros((K, P, P))
-        self.n_steps, self.iterations, self.evaluations = 0, 0, 0
-        self.min_margin, self.ndecisions, self._decisions = np.inf, 0, None
 
     # ---- set-up (dl_smc_set_hyper / set_particles / set_state / get_state / get_decisions) ----------------------------------------------------------------------------
     def set_hyper(self, ess_fraction, n_steps, target_acceptance, scale=1.):
         _check_hyper(ess_fraction, n_steps, target_acceptance, scale)
         self.ess_fraction, self.n_steps, self.target_acceptance = float(ess_fraction), int(n_steps), float(target_acceptance)
         self.scale[:] = scale
-
-    def _eval(self, x):
-        L, pi = self.f(np.ascontiguousarray(x.reshape(-1, self.P)))
-        self.evaluations += x.shape[0] * x.shape[1]
-        return np.array(L, dtype='f8').reshape(x.shape[:2]), np.array(pi, dtype='f8').reshape(x.shape[:2])
 
     def set_particles(self, coords):
         coords = np.array(coords, dtype='f8').reshape(self.K, self.N, self.P)
@@ -207,15 +193,7 @@ class _HostSMC(object):
     def get_state(self):
         return tuple(a.copy() for a in (self.x, self.L, self.pi, self.beta, self.logz, self.iter, self.scale, self.chol))
 
-    def get_decisions(self):
-        return self._decisions
-
     # ---- an iteration -------------------------------------------------------------------------------------------------------------------------------------------
-    def _margin(self, margins):
-        if len(margins):
-            self.min_margin = min(self.min_margin, float(np.min(margins)))
-            self.ndecisions += len(margins)
-
     def _iteration(self, rec):
         hist, coords, logp, count, quota = rec
         K, N, P, n = self.K, self.N, self.P, self.n_steps
@@ -232,7 +210,7 @@ class _HostSMC(object):
             self.beta[k] = level['beta']; self.logz[k] += level['dlogz']
             mean[k], cov[k] = moments(self.x[k], W)
             self.chol[k] = factor(cov[k], self.widths)
-            anc[k], margins = ancestors(W, self.draws.resample_uniform(self.iter[k], self.system_ids[k]))
+            anc[k], margins = ancestors(W, self.draws.resample_uniform(self.iter[k], self.ids[k]))
             self._margin(margins)
             self.x[k], self.L[k], self.pi[k] = self.x[k][anc[k]], self.L[k][anc[k]], self.pi[k][anc[k]]
         s, total = self.scale.copy(), np.zeros(K)
@@ -240,11 +218,11 @@ class _HostSMC(object):
         for j in range(n):
             prop = self.x.copy()
             for k in active:
-                z = self.draws.gauss(self.iter[k], j, self.system_ids[k], N, P)
+                z = self.draws.gauss(self.iter[k], j, self.ids[k], N, P)
                 prop[k] = self.x[k] + (s[k] * (2.38 / np.sqrt(float(P)))) * _matvec(self.chol[k], z)
             Lp, pip = self._eval(prop)
             for k in active:
-                logu = self.draws.log_uniform(self.iter[k], j, self.system_ids[k], N)
+                logu = self.draws.log_uniform(self.iter[k], j, self.ids[k], N)
                 ok = _live(Lp[k]) & _live(pip[k])
                 with np.errstate(invalid='ignore'):
                     ratio = self.beta[k] * (np.where(ok, Lp[k], 0.) - self.L[k]) + (np.where(ok, pip[k], 0.) - self.pi[k])
@@ -275,72 +253,25 @@ class _HostSMC(object):
         for _ in range(int(niterations)): self._iteration(tuple(buffers) + (int(quota),))
         self.iterations += int(niterations)
 
-    def counts(self, buffers):
-        return np.asarray(buffers[3])
 
-    def records(self, buffers):
-        return tuple(np.asarray(b) for b in buffers[:3])
-
-
-class _DeviceSMC(object):
-    """Systems resident on the GPU (``dl_smc_*``)."""
-    device_resident = True
+class _DeviceSMC(_DeviceEngine):
+    """Systems resident on the GPU (``dl_smc_*``): the calls of :class:`_HostSMC` go to the owner ``smc``."""
+    _counters = ('iterations', 'evaluations')
 
     def __init__(self, ctx, offset, nsystems, nparticles, widths, system_ids=None, seed=0):
         from ._lib import DeviceSMC
-        self.smc = DeviceSMC(ctx, nsystems, nparticles, widths, system_ids=system_ids, seed=seed, offset=offset)
+        self.smc = self._owner = DeviceSMC(ctx, nsystems, nparticles, widths, system_ids=system_ids, seed=seed, offset=offset)
         self.K, self.N, self.P = int(nsystems), int(nparticles), self.smc.n_params
-
-    def set_hyper(self, ess_fraction, n_steps, target_acceptance, scale=1.):
-        self.smc.set_hyper(ess_fraction, n_steps, target_acceptance, scale)
-
-    def set_particles(self, coords):
-        self.smc.set_particles(coords)
-
-    def set_state(self, *state):
-        self.smc.set_state(*state)
-
-    def get_state(self):
-        return self.smc.get_state()
-
-    def get_decisions(self):
-        return self.smc.get_decisions()
-
-    def buffers(self, quota):
-        return self.smc.buffers(quota)
-
-    def run(self, niterations, quota, buffers):
-        self.smc.run(niterations, quota, buffers)
-
-    def counts(self, buffers):
-        return buffers[3].cpu().numpy()        # the one synchronisation of a chunk
-
-    def records(self, buffers):
-        return tuple(b.cpu().numpy() for b in buffers[:3])
-
-    @property
-    def iterations(self):
-        return self.smc.info('iterations')
-
-    @property
-    def evaluations(self):
-        return self.smc.info('evaluations')
 
 
 def run_batch(engine, niterations, chunk=None):
     """``niterations`` iterations of every system in chunks of at most ``chunk``: (history [K, n, 5], coords [K, n, N, P], logposterior [K, n, N], counts [K, 2]);
     rows of coords / logposterior beyond counts[k, 1] are not written."""
-    niterations = int(niterations)
-    buffers = engine.buffers(max(niterations, 1))
-    left = niterations
-    while left > 0:
-        step = left if chunk is None else min(int(chunk), left)
-        engine.run(step, niterations, buffers)
-        left -= step
+    buffers = _run_chunks(engine, niterations, chunk)
     return engine.records(buffers) + (engine.counts(buffers).copy(),)
 
 
-class SMCSampler(BasePosteriorSampler):
+class SMCSampler(_EvidenceSampler):
     """``SMCSampler(likelihood, nparticles=1024, chains=1, ess_fraction=0.5, n_steps='2 * ndim', target_acceptance=0.234, seed=None, save_fn=None, device_resident=None)``:
     adaptive tempered sequential Monte Carlo from the PRIOR to the posterior, with the Bayesian evidence.
 
@@ -357,62 +288,22 @@ class SMCSampler(BasePosteriorSampler):
     (logsumexp(logz) - log chains: not the mean of the logs), ``logz_std`` (the scatter of ``logz``; ``None`` for one system), ``history`` (dict of [chains, T] arrays:
     beta, logz, ess, acceptance, scale), ``nevaluations``, ``chains`` (per system name -> [sweeps, nparticles] with ``logposterior``: the layout of
     :class:`~desilike_amd.samplers.EmceeSampler`)."""
-    name = 'smc'
+    name, _words = 'smc', ('SMCSampler', 'particles', 'system')
 
     def __init__(self, likelihood, nparticles=1024, chains=1, ess_fraction=0.5, n_steps='2 * ndim', target_acceptance=0.234, seed=None, save_fn=None, device_resident=None,
                  **kwargs):
         super(SMCSampler, self).__init__(likelihood, seed=seed, **kwargs)
-        if self.sharding.active and self.sharding.world > 1:
-            raise NotImplementedError('SMCSampler keeps all particles of a system on one GPU: run one sampler per rank (different seeds) and pool their logz')
-        ndim = len(self.varied_params)
-        if not 1 <= ndim <= 64: raise ValueError('SMCSampler takes 1 .. 64 varied parameters, found {:d}'.format(ndim))
-        resume = None
-        if not isinstance(chains, (int, np.integer)):
-            resume = [chains] if isinstance(chains, (str, dict)) or hasattr(chains, 'arrays') else list(chains)
-            chains = len(resume)
-        self.nchains, self.nparticles = int(chains), int(nparticles)
-        if self.nchains < 1: raise ValueError('chains must be >= 1')
+        resume = self._setup(chains, seed, save_fn, device_resident)
+        ndim, self.nparticles = len(self.varied_params), int(nparticles)
         _check_particles(self.nparticles)
-        if isinstance(n_steps, str): n_steps = int(eval(n_steps, {'ndim': ndim}))
-        self.ess_fraction, self.n_steps, self.target_acceptance = float(ess_fraction), int(n_steps), float(target_acceptance)
+        self.ess_fraction, self.n_steps, self.target_acceptance = float(ess_fraction), int(_expression(n_steps, ndim=ndim)), float(target_acceptance)
         _check_hyper(self.ess_fraction, self.n_steps, self.target_acceptance, 1.)
-        for param in self.varied_params:
-            if not param.prior.is_proper():
-                raise ValueError('SMCSampler draws its particles from the priors: the prior of {} is not proper'.format(param.name))
-        self.widths = np.array([param.prior.limits[1] - param.prior.limits[0] if param.prior.dist == 'uniform' else param.prior.std() for param in self.varied_params], dtype='f8')
-        if device_resident is None:
-            device_resident = getattr(likelihood, '_get_posterior_context', None) is not None and not len(getattr(likelihood, 'dependent_params', []))
-        self.device_resident = bool(device_resident)
-        if seed is None: seed = int(self.rng.randint(0, 2**32, dtype=np.uint64))
-        self.counter_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        if save_fn is not None:
-            if isinstance(save_fn, str): save_fn = [save_fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-            save_fn = list(save_fn)
-            if len(save_fn) != self.nchains or len(set(save_fn)) != self.nchains: raise ValueError('provide one file name per chain (or a template with *)')
-        self.save_fn = save_fn
-        self._engine, self._state = None, None
         self._history = np.zeros((self.nchains, 0, 5))
         self._coords = [np.zeros((0, self.nparticles, ndim)) for _ in range(self.nchains)]
         self._logp = [np.zeros((0, self.nparticles)) for _ in range(self.nchains)]
-        self._evaluations = 0
         if resume is not None: self._resume(resume)
 
     # ---- engine -------------------------------------------------------------------------------------------------------------------------------------------------
-    def _host_terms(self, values):
-        """(loglike, logprior) of rows through the likelihood's own call surface (likelihoods without a device context)."""
-        from .parameter import Samples
-        values = np.atleast_2d(values)
-        logprior = self.logprior(values)
-        loglike = np.full(values.shape[0], -np.inf)
-        finite = np.isfinite(logprior) & ~np.isnan(values).any(axis=1)
-        if finite.any():
-            (_, derived), errors = self._vlikelihood(Samples(values[finite].T, params=self.varied_params).to_dict())
-            column = np.array(derived[self.likelihood._param_loglikelihood], dtype='f8')
-            column[np.isnan(column)] = -np.inf
-            for ipoint in errors: column[ipoint] = -np.inf
-            loglike[finite] = column
-        return loglike, logprior
-
     def _make_engine(self):
         ids, ndim = np.arange(self.nchains), len(self.varied_params)
         if self.device_resident:
@@ -485,37 +376,17 @@ class SMCSampler(BasePosteriorSampler):
         if not self._history.shape[1]: return np.full(self.nchains, np.nan)
         return self._history[:, -1, 1].copy()
 
-    @property
-    def logz_mean(self):
-        logz = self.logz
-        top = logz.max()
-        return float(top + np.log(np.mean(np.exp(logz - top))))
-
-    @property
-    def logz_std(self):
-        return float(np.std(self.logz, ddof=1)) if self.nchains > 1 else None
-
-    @property
-    def nevaluations(self):
-        return int(self._evaluations)
-
     def save(self, fn=None):
         """One file per system in the reference's checkpoint format; attributes ``{'sampler': 'smc', 'seed', 'state', 'history', ...}``: the state continues the run."""
-        from .io import ChainFile
-        if fn is None: fn = self.save_fn
-        if fn is None: raise ValueError('provide a file name')
-        if isinstance(fn, str): fn = [fn.replace('*', str(ichain)) for ichain in range(self.nchains)]
-        if len(fn) != self.nchains: raise ValueError('provide one file name per chain')
+        fn = self._save_names(fn)
         if self._state is None: return
-        for k, (chain, name) in enumerate(zip(self.chains, fn)):
-            attrs = {'sampler': self.name, 'seed': self.counter_seed, 'system': k, 'state': [np.asarray(a[k]) for a in self._state], 'history': self._history[k],
-                     'hyper': [self.ess_fraction, self.n_steps, self.target_acceptance], 'evaluations': self._evaluations}
-            ChainFile(dict(chain), params={param.name: param for param in self.varied_params}, attrs=attrs).save(name)
+        self._write_chains((name, chain, {'sampler': self.name, 'seed': self.counter_seed, 'system': k, 'state': [np.asarray(a[k]) for a in self._state], 'history': self._history[k],
+                                          'hyper': [self.ess_fraction, self.n_steps, self.target_acceptance], 'evaluations': self._evaluations})
+                           for k, (chain, name) in enumerate(zip(self.chains, fn)))
 
     def _resume(self, sources):
         """Continue the systems saved by :meth:`save`: particles, temperatures, evidences, counters, scales, factors (and the records so far)."""
-        from .io import ChainFile
-        files = [s if hasattr(s, 'arrays') else ChainFile.load(s) for s in sources]
+        files = _open_chain_files(sources)
         names = self.varied_params.names()
         for f in files:
             if f.attrs.get('sampler', None) != self.name or 'state' not in f.attrs: raise ValueError('not a chain file of SMCSampler')

@@ -573,9 +573,16 @@ def solve_marginalized(flatdiff, flatderiv, precision, x0, prior_loc, prior_scal
     """
     flatdiff, flatderiv = np.asarray(flatdiff, dtype='f8'), np.atleast_2d(np.asarray(flatderiv, dtype='f8'))
     x0, prior_loc, prior_scale = (np.asarray(a, dtype='f8') for a in (x0, prior_loc, prior_scale))
-    derivp = flatderiv * precision if precision.ndim == 1 else flatderiv.dot(precision)   # 169-172
-    likelihood_gradient = -derivp.dot(flatdiff.T)                                          # 173
-    likelihood_hessian = -derivp.dot(flatderiv.T)                                          # 174
+    # The sums over the data (T P Delta, T P T^T, Delta P Delta) are accumulated in long double and rounded to float64 once, like the value, which is assembled from
+    # -chi2(x0) / 2 and two quadratic forms that cancel most of it, so the rounding of an n x n float64 accumulation enters in absolute terms, eps n chi2(x0) -- 1.0e-12 of the
+    # result on fixture marg_sn0_grid (chi2(x0) = 1.8e4, n = 120) against the extended-precision reference of tests/marg_reference.py.  Where long double is double, as before.
+    wide = np.longdouble
+    precision = np.asarray(precision, dtype='f8')
+    flatdiff_w, flatderiv_w, precision_w = flatdiff.astype(wide), flatderiv.astype(wide), precision.astype(wide)
+    derivp = flatderiv_w * precision_w if precision.ndim == 1 else flatderiv_w.dot(precision_w)   # 169-172
+    gradient_w, hessian_w, chi2_w = -derivp.dot(flatdiff_w.T), -derivp.dot(flatderiv_w.T), chi2(flatdiff_w, precision_w)
+    likelihood_gradient = gradient_w.astype('f8')                                           # 173
+    likelihood_hessian = hessian_w.astype('f8')                                             # 174
     prec = prior_scale**(-2)                                                               # 181
     prior_gradient = -(x0 - prior_loc) * prec                                              # 182
     prior_hessian = np.diag(-prec)                                                         # 183-185
@@ -583,8 +590,8 @@ def solve_marginalized(flatdiff, flatderiv, precision, x0, prior_loc, prior_scal
     posterior_hessian = prior_hessian + likelihood_hessian
     dx = -np.linalg.solve(posterior_hessian, posterior_gradient)                           # 188
     x = x0 + dx                                                                            # 189
-    loglikelihood = -0.5 * chi2(flatdiff, precision)
-    loglikelihood += 0.5 * dx.dot(likelihood_hessian).dot(dx) + likelihood_gradient.dot(dx)   # 385-386
+    dx_w = dx.astype(wide)
+    loglikelihood = float(-0.5 * chi2_w + 0.5 * dx_w.dot(hessian_w).dot(dx_w) + gradient_w.dot(dx_w))   # 385-386 (the three terms cancel: summed before rounding)
     # prior of the solved parameters at their solution, zero-lag removed (363-364, parameter.py:2003-2010)
     logprior = np.sum(np.where(np.isinf(prior_scale), 0., -0.5 * (x - prior_loc)**2 * prec))
     marg_mask = np.asarray(marg_mask, dtype='?')

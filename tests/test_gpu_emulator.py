@@ -25,7 +25,7 @@ def test_taylor_emulated_velocileptors_vs_reference():
     assert np.allclose(like.flattheory, g['flattheory'][:3], rtol=1e-11, atol=1e-8)
 
 
-def make_mlp_likelihood(marg=True, seed=1, derived=None, hidden=(64, 64, 64), activation='silu'):
+def make_mlp_likelihood(marg=True, seed=1, derived=None, hidden=(64, 64, 64), activation='silu', prior_basis='physical'):
     from desilike_amd.emulators import EmulatedCalculator, MLPEmulatorEngine
     from desilike_amd.theories.galaxy_clustering import LPTVelocileptorsTracerPowerSpectrumMultipoles
     from desilike_amd.observables.galaxy_clustering import TracerPowerSpectrumMultipolesObservable
@@ -55,12 +55,12 @@ def make_mlp_likelihood(marg=True, seed=1, derived=None, hidden=(64, 64, 64), ac
     specs = {'qpar': dict(value=1., prior=dict(limits=[0.8, 1.2]), ref=dict(limits=[0.98, 1.02])), 'qper': dict(value=1., prior=dict(limits=[0.8, 1.2]), ref=dict(limits=[0.98, 1.02])),
              'dm': dict(value=0., prior=dict(limits=[-1., 1.]), ref=dict(limits=[-0.05, 0.05]))}
     pt = EmulatedCalculator(EMU_PARAMS, engines, k=kpt, ells=(0, 2, 4), z=0.8, param_specs=specs)
-    theory = LPTVelocileptorsTracerPowerSpectrumMultipoles(pt=pt, tracer='ELG')
+    theory = LPTVelocileptorsTracerPowerSpectrumMultipoles(pt=pt, tracer='ELG', prior_basis=prior_basis)
     solved = ['alpha0p', 'alpha2p', 'alpha4p', 'sn0p', 'sn2p'] if marg else []
     if derived is not None: solved = list(derived)
     for name in solved:
         theory.init.params[name].update(derived='.marg' if derived is None else derived[name])
-    theory.init.params['sn4p'].update(fixed=True, value=0.3)
+    theory.init.params['sn4p' if prior_basis == 'physical' else 'sn4'].update(fixed=True, value=0.3)
     obs = TracerPowerSpectrumMultipolesObservable(data=g['obs0']['flatdata'], kedges=np.linspace(0.02, 0.2, 37), ells=(0, 2, 4), wmatrix={'resolution': 2}, theory=theory, shotnoise=8e3)
     like = ObservablesGaussianLikelihood(observables=[obs], covariance=g['covariance'])
     return g, like, pt, theory, solved

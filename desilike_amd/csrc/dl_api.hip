@@ -59,6 +59,8 @@ struct dl_ctx {
     // workspaces (grown on demand, never inside dl_eval_* once large enough)
     int64_t cap = 0;
     double* power_ws = nullptr;      // [cap, K_pad]
+    double* ws_scratch = nullptr;    // [cap, ws_ld] wiggle-split templates (kind 5, dl_wigglesplit.h) at the knots: written by the template kernel, copied by the theory kernels
+    int64_t ws_ld = 0;               // doubles per point: the knot counts of the distinct templates (0: no such template)
     double* delta_ws = nullptr;      // [cap, N_pad]
     double* flat_ws = nullptr;       // [cap, N_pad]  (transform path / flattheory staging)
     double* stencil_ws = nullptr;    // [cap, n_params] theta rows of the Fisher stencil
@@ -214,6 +216,17 @@ int dl_create(dl_ctx** out, int device, const dl_config* cfg) {
         row += ctx->obs[i].n_out;
         ctx->max_n_t = std::max(ctx->max_n_t, ctx->obs[i].dev.n_t);
         if (ctx->obs[i].dev.transform != 0) ctx->any_transform = true;
+    }
+    // wiggle-split templates: observables whose template tables and inputs are equal share one evaluation per point (one block of columns of the scratch)
+    for (int i = 0; i < ctx->n_obs; ++i) {
+        DlObsHost& ob = ctx->obs[i];
+        if (ob.dev.templ != 5) continue;
+        auto same_input = [](const DlInput& a, const DlInput& b) { return a.col == b.col && (a.col >= 0 || a.value == b.value); };
+        for (int j = 0; j < i && ob.ws_leader < 0; ++j) {
+            const DlObsHost& other = ctx->obs[j];
+            if (other.dev.templ == 5 && other.ws_leader == j && other.ws_tab == ob.ws_tab && same_input(other.ws_qbao, ob.ws_qbao) && same_input(other.ws_dm, ob.ws_dm)) { ob.ws_leader = j; ob.ws_col = other.ws_col; }
+        }
+        if (ob.ws_leader < 0) { ob.ws_leader = i; ob.ws_col = ctx->ws_ld; ctx->ws_ld += (ob.dev.n_t + 1) & ~1; }
     }
     for (auto& ob : ctx->obs)
         if ((ob.dev.theory == 3 || ob.dev.theory == 4 ? 0 : ob.dev.theory == 5 ? dl_png_shared_doubles(ob.dev.n_t, ob.dev.n_in) : ob.dev.theory == 2 ? (ob.dev.templ == 4 ? dl_bao_ps_shared_doubles(ob.dev.n_t, ob.dev.n_in) : dl_bao_shared_doubles(ob.dev.n_in)) : dl_fs_shared_doubles(ob.dev.n_t, ob.dev.n_in)) * sizeof(double) > 160 * 1024)
@@ -507,7 +520,7 @@ void dl_destroy(dl_ctx* ctx) {
     if (ctx->ss_status) (void)hipFree(ctx->ss_status);
     void* ptrs[] = {ctx->arena_dev, ctx->priors_dev, ctx->wt_white_dev, ctx->wt_frag_dev, ctx->bias_white_dev, ctx->wt_full_dev, ctx->bias_full_dev, ctx->wh_dev,
                     ctx->bias_wh_dev, ctx->flatdata_dev, ctx->transform_dev, ctx->tconst_dev, ctx->power_ws, ctx->delta_ws, ctx->flat_ws, ctx->stencil_ws, ctx->theta_stage, ctx->out_stage,
-                    ctx->status_stage, ctx->gemm_counters, ctx->obs_array_dev};
+                    ctx->status_stage, ctx->gemm_counters, ctx->obs_array_dev, ctx->ws_scratch};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (double* p : ctx->gfrag_dev) if (p) (void)hipFree(p);
     for (auto& ob : ctx->obs) if (ob.tns) { dl_tns_destroy(ob.tns); ob.tns = nullptr; }
@@ -536,6 +549,7 @@ int64_t dl_info(const dl_ctx* ctx, const char* key) {
     if (k == "N_pad") return ctx->N_pad;
     if (k == "n_solved") return ctx->n_solved;
     if (k == "device") return ctx->device;
+    if (k == "ws_ld") return ctx->ws_ld;   // doubles per point of the wiggle-split template scratch: the knot counts (rounded up to even) of the DISTINCT templates
     for (int i = 0; i < ctx->n_obs; ++i) {
         if (k == "n_in_obs" + std::to_string(i)) return ctx->obs[i].dev.n_in;
         if (k == "n_out_obs" + std::to_string(i)) return ctx->obs[i].n_out;
@@ -553,7 +567,7 @@ static int dl_reserve(dl_ctx* ctx, int64_t B) {
     if (need <= ctx->cap) return 0;
     need = std::min<int64_t>(std::max<int64_t>(need, 1024), DL_CHUNK);
     if (ctx->cap > 0) DL_HIP_CHECK(ctx, hipDeviceSynchronize());   // kernels of earlier calls (any stream) may still read the workspaces about to be freed
-    for (double** p : {&ctx->power_ws, &ctx->delta_ws, &ctx->flat_ws, &ctx->feat_ws, &ctx->stencil_ws}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (double** p : {&ctx->power_ws, &ctx->delta_ws, &ctx->flat_ws, &ctx->feat_ws, &ctx->stencil_ws, &ctx->ws_scratch}) if (*p) { (void)hipFree(*p); *p = nullptr; }
     ctx->cap = 0;
     const size_t R = 1 + ctx->n_var;   // rows per point: power + point-dependent derivative rows (analytic marginalisation)
     DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->power_ws, (size_t)need * R * ctx->K_pad * sizeof(double)));
@@ -562,6 +576,17 @@ static int dl_reserve(dl_ctx* ctx, int64_t B) {
     DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->flat_ws, (size_t)need * ctx->N_pad * sizeof(double)));
     if (ctx->feat_ok) DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->feat_ws, (size_t)need * ctx->feat_ld * sizeof(double)));
     DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->stencil_ws, (size_t)need * ctx->n_params * sizeof(double)));
+    if (ctx->ws_ld > 0) {
+        // the template scratch moved: the observables' descriptions (host copies and the device array of the merged launches) point at their blocks of it
+        DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ws_scratch, (size_t)need * ctx->ws_ld * sizeof(double)));
+        DL_HIP_CHECK(ctx, hipMemset(ctx->ws_scratch, 0, (size_t)need * ctx->ws_ld * sizeof(double)));
+        for (int i = 0; i < ctx->n_obs; ++i) {
+            if (ctx->obs[i].dev.templ != 5) continue;
+            ctx->obs_kernarg[i].coef_w = ctx->ws_scratch + ctx->obs[i].ws_col;   // (dl_ws_scratch)
+            ctx->obs_kernarg[i].n_band = (int32_t)ctx->ws_ld;                    // (dl_ws_scratch_ld)
+        }
+        DL_HIP_CHECK(ctx, hipMemcpy(ctx->obs_array_dev, ctx->obs_kernarg.data(), ctx->obs_kernarg.size() * sizeof(DlObsDev), hipMemcpyHostToDevice));
+    }
     // the K padding columns of the power buffer are never written by the theory kernel and must be finite (they meet zeros of the operators); the other
     // workspaces are zeroed too: recycled device memory holds whatever the previous owner left, and 0 x NaN is NaN
     DL_HIP_CHECK(ctx, hipMemset(ctx->power_ws, 0, (size_t)need * R * ctx->K_pad * sizeof(double)));
@@ -1109,6 +1134,8 @@ int dl_eval_theory(dl_ctx* ctx, const double* theta_dev, int64_t B, int32_t iobs
     if (B == 0) return 0;
     hipStream_t stream = (hipStream_t)hip_stream;
     DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const bool ws = ctx->obs_kernarg[iobs].templ == 5;   // wiggle-split template: its kernel writes the context's scratch, in passes of at most its capacity
+    if (ws && dl_reserve(ctx, B)) return 1;
     // launch only observable iobs, writing rows of n_in doubles directly into the caller's buffers
     DlObsDev tmp = ctx->obs_kernarg[iobs];
     tmp.col_offset = 0;
@@ -1117,7 +1144,9 @@ int dl_eval_theory(dl_ctx* ctx, const double* theta_dev, int64_t B, int32_t iobs
     for (int c = 0; c < DL_N_VPARS; ++c) tmp.vp_slot[c] = -1;
     for (int c = 0; c < DL_MAX_EFT; ++c) tmp.marg_ct_slot[c][0] = tmp.marg_ct_slot[c][1] = -1;
     if (dl_order_streams(ctx, stream)) return 1;
-    dl_launch_fullshape(&tmp, 1, theta_dev, ctx->n_params, B, power_dev, tmp.n_in, tables_dev, 3 * (int64_t)tmp.n_in, stream);
+    for (int64_t b0 = 0, step = ws ? ctx->cap : B; b0 < B; b0 += step)
+        dl_launch_fullshape(&tmp, 1, theta_dev + (size_t)b0 * ctx->n_params, ctx->n_params, std::min(step, B - b0), power_dev + (size_t)b0 * tmp.n_in, tmp.n_in,
+                            tables_dev ? tables_dev + (size_t)b0 * 3 * tmp.n_in : nullptr, 3 * (int64_t)tmp.n_in, stream);
     DL_HIP_CHECK(ctx, hipGetLastError());
     return 0;
 }

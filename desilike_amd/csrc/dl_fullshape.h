@@ -122,7 +122,7 @@ struct DlObsDev {
     double res_sig[4];                     // resummed wiggles: sigma_dd^2, sigma_nl^2, sigma_x^2, shotnoise * sigma_sn^2 (bao.py:186-199)
     // flexible wiggles (bao.py:269-391): terms ml_i K_i(k) L_{ell_i}(mu) multiplying the wiggles; K [n_ml, n_kin] sits behind ct_matrix, the Legendre
     // polynomials L_ell(mu) [n_ell, n_mu] behind sn_matrix (both unused by the BAO kernels otherwise)
-    int32_t n_ml, pad_ml;
+    int32_t n_ml, pad_ml;                  // (pad_ml: inner knot count of the wiggle-split template, kind 5 -- read by the launcher only)
     const double* ml_tab;                  // [n_ml][3]: theta column (or -1), constant value, index (in ells_in) of the term's multipole -- in the arena, not in
                                            // the kernarg segment (the struct travels by value with every launch of every theory kernel)
     double smoothing_radius;
@@ -351,7 +351,13 @@ DL_HD void dl_fs_scalars(const DlObsDev& o, const double* th, const DlFsShared& 
 }
 
 // template at the knots (or the fixed interval polynomials), nthr threads
-DL_HD void dl_fs_knots(int tid, int nthr, const DlObsDev& o, const double* th, const DlFsShared& s) {
+// b: the point's index in the batch (wiggle-split template only: its row of the template scratch, see dl_wigglesplit.h)
+DL_HD const double* dl_ws_scratch(const DlObsDev& o) { return o.coef_w; }     // template kind 5 (Kaiser-type theories: no BAO wiggle spline) borrows the BAO kernel's pointer
+DL_HD int64_t dl_ws_scratch_ld(const DlObsDev& o) { return o.n_band; }          // ... and the band count: doubles per point of the scratch
+// WS: the branch of the wiggle-split template is compiled in -- only where that template can arrive (the full-shape kernel's forms without the moment form, dl_kernels.hip:
+// dl_fullshape_body); every other caller keeps the code it had
+template <bool WS = false>
+DL_HD void dl_fs_knots(int tid, int nthr, const DlObsDev& o, const double* th, const DlFsShared& s, int64_t b = 0) {
     const int n_t = o.n_t;
     if (o.toeplitz && !o.fixed_spline && tid < 2 * DL_FIR_PAD) s.y[tid < DL_FIR_PAD ? tid - DL_FIR_PAD : n_t + tid - DL_FIR_PAD] = 0.;   // zero padding
     if (o.fixed_spline) {
@@ -376,6 +382,10 @@ DL_HD void dl_fs_knots(int tid, int nthr, const DlObsDev& o, const double* th, c
             for (int i = 0; i < o.n_band; ++i) factor += (dl_get(o.band_in[i], th) - 1.) * o.band_tab[(size_t)i * n_t + j];   // (n_band is 0 for template kind 4, which borrows band_in[0] / band_tab: dl_ps_baoshift)
             s.y[j] = o.pk_fid[j] * factor * inv_df2;
         }
+    } else if (WS && o.templ == 5) {
+        // power_template.py:1193-1202: the point's P_dd at the knots, left in the template scratch by the template kernel (dl_ws_template_kernel) that ran before
+        const double* row = dl_ws_scratch(o) + (size_t)b * dl_ws_scratch_ld(o);
+        for (int j = tid; j < n_t; j += nthr) s.y[j] = row[j];
     } else {
         for (int j = tid; j < n_t; j += nthr) s.y[j] = o.pk_fid[j];
     }
@@ -398,7 +408,8 @@ DL_HD void dl_fs_knots_rec(int tid, int nthr, const DlObsDev& o, const double* t
 }
 
 // the whole of phase 0 + 1 in one call (general kernel, host-side constant folding): mu nodes on the last threads, scalars on thread 0
-DL_HD void dl_fs_phase01(int tid, int nthr, const DlObsDev& o, const double* th, const DlFsShared& s) {
+template <bool WS = false>
+DL_HD void dl_fs_phase01(int tid, int nthr, const DlObsDev& o, const double* th, const DlFsShared& s, int64_t b = 0) {
     const int mnode = nthr - 1 - tid;
     if (mnode < o.n_mu || tid == 0) {
         DlMuCarry c;
@@ -406,7 +417,7 @@ DL_HD void dl_fs_phase01(int tid, int nthr, const DlObsDev& o, const double* th,
         if (mnode < o.n_mu) { dl_fs_mu_partB(c); dl_fs_mu_partC(o, s, mnode, c); }
         if (tid == 0) dl_fs_scalars(o, th, s, c);
     }
-    dl_fs_knots(tid, nthr, o, th, s);
+    dl_fs_knots<WS>(tid, nthr, o, th, s, b);
 }
 
 // phase 2a: right-hand side of the reduced (n_t - 2 unknowns) not-a-knot system, pre-multiplied by the pivots
@@ -1110,9 +1121,8 @@ DL_HD void dl_bao_ps_knots(int tid, int nthr, const DlObsDev& o, const double* t
 
 // m_j = sum_e t_|e| y_{j+e}: the solution of m_{j-1} + 4 m_j + m_{j+1} = y_{j-1} - 2 y_j + y_{j+1} on the infinite grid (see dl_fs_phase2_fir); four consecutive knots
 // per thread from one sliding window
-DL_HD void dl_bao_ps_fir(int tid, int nthr, const DlObsDev& o, const DlPsShared& s) {
+DL_HD void dl_ps_fir(int tid, int nthr, int n, const DlPsShared& s) {   // n knots (the wiggle-split template runs it on its inner grid: dl_wigglesplit.h)
     const double T[DL_FIR_D + 1] = DL_FIR_TAPS;
-    const int n = o.n_t;
     for (int j0 = 4 * tid; j0 < n; j0 += 4 * nthr) {
         double acc[4] = {0., 0., 0., 0.};
         const double* yp = s.y + j0 - DL_FIR_D;   // knot j0 - D + p: down to y[-DL_FIR_D], up to y[n + 2 + DL_FIR_D] (inside the padding)
@@ -1130,28 +1140,32 @@ DL_HD void dl_bao_ps_fir(int tid, int nthr, const DlObsDev& o, const DlPsShared&
             if (j0 + q < n) s.m[j0 + q] = acc[q];
     }
 }
+DL_HD void dl_bao_ps_fir(int tid, int nthr, const DlObsDev& o, const DlPsShared& s) { dl_ps_fir(tid, nthr, o.n_t, s); }
 
 // End corrections: m_j += a mu^(j-1) + b mu^(n-2-j) with a, b from the not-a-knot rows m_1 = r_1 / 6, m_{n-2} = r_{n-2} / 6 (dl_fs_phase2d_toep, in units of h^2 / 6).
 // Threads 0 .. 2 DL_FIR_PAD - 1 (every workgroup has at least 64) take one knot each: 1 .. DL_FIR_PAD from the left, n-2 .. n-1-DL_FIR_PAD from the right (n >= 4
 // DL_FIR_PAD: disjoint; beyond them the correction is below rounding).  a and b read m_1 and m_{n-2}, which are themselves corrected: every thread computes its value
 // (dl_bao_ps_end_moment), a barrier, then the stores (dl_bao_ps_end_store), a barrier, then the end relations for m_0, m_{n-1} (dl_bao_ps_end_relations).
 DL_HD int dl_bao_ps_end_knot(int tid, int n) { return tid < DL_FIR_PAD ? 1 + tid : n - 2 - (tid - DL_FIR_PAD); }
-DL_HD double dl_bao_ps_end_moment(int tid, const DlObsDev& o, const DlPsShared& s) {
+DL_HD double dl_ps_end_moment(int tid, int n, const DlPsShared& s) {
     if (tid >= 2 * DL_FIR_PAD) return 0.;
-    const int n = o.n_t, i = dl_bao_ps_end_knot(tid, n);
+    const int i = dl_bao_ps_end_knot(tid, n);
     const double a = ((s.y[0] - s.y[1]) - (s.y[1] - s.y[2])) * (1. / 6.) - s.m[1];
     const double b = ((s.y[n - 3] - s.y[n - 2]) - (s.y[n - 2] - s.y[n - 1])) * (1. / 6.) - s.m[n - 2];
     const int kl = i - 1, kr = n - 2 - i;
     return s.m[i] + a * (kl <= 2 * DL_FIR_PAD ? s.mupow[kl] : 0.) + b * (kr <= 2 * DL_FIR_PAD ? s.mupow[kr] : 0.);
 }
-DL_HD void dl_bao_ps_end_store(int tid, const DlObsDev& o, const DlPsShared& s, double value) {
-    if (tid < 2 * DL_FIR_PAD) s.m[dl_bao_ps_end_knot(tid, o.n_t)] = value;
+DL_HD void dl_ps_end_store(int tid, int n, const DlPsShared& s, double value) {
+    if (tid < 2 * DL_FIR_PAD) s.m[dl_bao_ps_end_knot(tid, n)] = value;
 }
-DL_HD void dl_bao_ps_end_relations(int tid, const DlObsDev& o, const DlPsShared& s) {
-    const int n = o.n_t;
-    if (tid == 0) s.m[0] = o.end0a * s.m[1] + o.end0b * s.m[2];
-    if (tid == 1) s.m[n - 1] = o.end1a * s.m[n - 2] + o.end1b * s.m[n - 3];
+DL_HD void dl_ps_end_relations(int tid, int n, double end0a, double end0b, double end1a, double end1b, const DlPsShared& s) {
+    if (tid == 0) s.m[0] = end0a * s.m[1] + end0b * s.m[2];
+    if (tid == 1) s.m[n - 1] = end1a * s.m[n - 2] + end1b * s.m[n - 3];
 }
+// (the BAO kernel's own spline: the template knots of the observable)
+DL_HD double dl_bao_ps_end_moment(int tid, const DlObsDev& o, const DlPsShared& s) { return dl_ps_end_moment(tid, o.n_t, s); }
+DL_HD void dl_bao_ps_end_store(int tid, const DlObsDev& o, const DlPsShared& s, double value) { dl_ps_end_store(tid, o.n_t, s, value); }
+DL_HD void dl_bao_ps_end_relations(int tid, const DlObsDev& o, const DlPsShared& s) { dl_ps_end_relations(tid, o.n_t, o.end0a, o.end0b, o.end1a, o.end1b, s); }
 
 // wiggle on interval j at the fractional index u (0 <= j <= n_t - 2; u outside [0, 1] continues the end pieces):
 //   S = y_j + u [(y_j+1 - y_j) - (2 m_j + m_j+1) + u (3 m_j + u (m_j+1 - m_j))]

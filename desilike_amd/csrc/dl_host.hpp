@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "dl_fullshape.h"
+#include "dl_wigglesplit.h"
 #include "dl_tns.h"
 
 struct dl_config {
@@ -69,6 +70,12 @@ struct DlObsHost {
     int marg_vp[DL_N_VPARS];
     int marg_pass[DL_MAX_PASS];
     int n_cols() const { return dev.n_in + dev.n_pass; }   // columns of this observable in the theory vector / window matrix
+    // wiggle-split template (kind 5): its constant tables and inputs (observables with equal ones share ONE evaluation per point), the first column of its row in the
+    // template scratch and the first observable with the same template (itself: this one launches the template kernel)
+    std::vector<double> ws_tab;
+    DlInput ws_qbao, ws_dm;
+    int64_t ws_col = 0;
+    int ws_leader = -1;
 
     void rebase(const double* base) {
         dev.kin = base + off_kin; dev.lkin = base + off_lkin; dev.mu = base + off_mu; dev.wmu = base + off_wmu;
@@ -166,6 +173,122 @@ inline DlInput dl_input_from(const dl_config& cfg, const std::string& key, doubl
     const auto& v = cfg.F(key);
     if (v.size() >= 2) { in.col = (int32_t)std::lround(v[0]); in.value = v[1]; }
     return in;
+}
+
+// ---- wiggle-split template (template kind 5, dl_wigglesplit.h): the constant tables of dl_ws_tab ---------------------------------------------------------------
+// interval polynomials [n - 1][4], in the fractional index of the exactly uniform grid, of the not-a-knot spline of log10 y over log10 k (k uniform in log10 k)
+inline bool dl_ws_loglog_polynomials(const std::vector<double>& k, const std::vector<double>& y, const std::string& what, std::vector<double>& coef, double& x0, double& inv_h,
+                                     std::string& err) {
+    const int n = (int)k.size();
+    if (n < 5 || (int)y.size() != n) { err = what + ": at least 5 wavenumbers, one value each"; return false; }
+    std::vector<double> x(n), ly(n), dlt(n), M;
+    for (int j = 0; j < n; ++j) {
+        if (!(k[j] > 0.) || !(y[j] > 0.)) { err = what + ": wavenumbers and power must be positive"; return false; }
+        x[j] = std::log10(k[j]); ly[j] = std::log10(y[j]);
+    }
+    DlSplineSetup sp;
+    if (!dl_spline_setup(x, sp, err)) { err = what + ": " + err; return false; }
+    DlObsDev tmp;
+    std::memset(&tmp, 0, sizeof(tmp));
+    tmp.n_t = n; tmp.uniform_knots = 1;
+    tmp.x0 = x[0]; tmp.inv_hx = (n - 1) / (x[n - 1] - x[0]);
+    tmp.end0a = sp.end0a; tmp.end0b = sp.end0b; tmp.end1a = sp.end1a; tmp.end1b = sp.end1b;
+    for (int j = 0; j < n; ++j) {
+        dlt[j] = x[j] - (tmp.x0 + j / tmp.inv_hx);
+        if (std::fabs(dlt[j] * tmp.inv_hx) > 1e-6) { err = what + ": the grid must be uniform in log k (geomspace)"; return false; }
+    }
+    dl_spline_moments_serial(ly, sp, M);
+    std::vector<double> lds(dl_fs_shared_doubles(n, 0), 0.);
+    DlFsShared sh = dl_fs_shared_carve(lds.data(), n, 0);
+    for (int j = 0; j < n; ++j) { sh.y[j] = ly[j]; sh.M[j] = M[j]; }
+    tmp.ih = sp.ih.data(); tmp.x_t = x.data(); tmp.dlt = dlt.data();
+    dl_fs_phase2d(0, 1, tmp, sh);
+    coef.assign((size_t)4 * (n - 1), 0.);
+    for (int j = 0; j < n - 1; ++j)
+        for (int q = 0; q < 4; ++q) coef[(size_t)4 * j + q] = sh.coef[(size_t)(q >> 1) * 2 * n + 2 * j + (q & 1)];
+    x0 = tmp.x0; inv_h = tmp.inv_hx;
+    return true;
+}
+
+// W^2(x) of integrate_sigma_r2 (power_template.py:973-1030): 0 Gaussian exp(-x^2), 1 top-hat [3 (sin x - x cos x) / x^3]^2 with its series below x = 0.1
+inline double dl_ws_kernel2(int kernel, double x) {
+    if (kernel == 0) return std::exp(-x * x);
+    double w;
+    if (x < 0.1) {
+        const double x2 = x * x;
+        w = 1. + x2 * (-1.0 / 10.0 + x2 * (1.0 / 280.0 + x2 * (-1.0 / 15120.0 + x2 * (1.0 / 1330560.0 + x2 * (-1.0 / 172972800.0)))));
+    } else w = 3. * (std::sin(x) - x * std::cos(x)) / (x * x * x);
+    return w * w;
+}
+
+inline bool dl_ws_build(const dl_config& cfg, const std::string& p, const DlObsDev& d, const std::vector<double>& k_t, std::vector<double>& tab, std::string& err) {
+    const std::string w = p + "wiggle-split template: ";
+    const auto& ki = cfg.F(p + "ws_k");
+    const auto& pknow_i = cfg.F(p + "ws_pknow");
+    const auto& kf = cfg.F(p + "ws_kfid");
+    const auto& ptt = cfg.F(p + "ws_pk_tt_fid");
+    const auto& pnow = cfg.F(p + "ws_pknow_tt_fid");
+    const double r = cfg.f(p + "ws_r", 8.), kp = cfg.f(p + "ws_kp", 0.05), fsigmar = cfg.f(p + "ws_fsigmar_fid", 0.);
+    const int kernel = cfg.i(p + "ws_kernel", 0);
+    const int n_i = (int)ki.size(), n_f = (int)kf.size(), n_q = DL_WS_NQ, n_t = d.n_t;
+    if (kernel != 0 && kernel != 1) { err = w + "ws_kernel is 0 (gauss) or 1 (tophat)"; return false; }
+    if (!(r > 0.) || !(kp > 0.) || !(fsigmar > 0.) || !(d.f_fid > 0.)) { err = w + "ws_r, ws_kp, ws_fsigmar_fid and f_fid must be positive"; return false; }
+    if (n_i < 4 * DL_FIR_PAD) { err = w + "the inner grid ws_k needs at least 128 knots (the convolution that inverts its spline system)"; return false; }
+    if ((int)pknow_i.size() != n_i) { err = w + "ws_pknow must have one entry per inner knot"; return false; }
+    std::vector<double> xi(n_i);
+    for (int j = 0; j < n_i; ++j) {
+        if (!(ki[j] > 0.) || !(pknow_i[j] > 0.)) { err = w + "ws_k and ws_pknow must be positive"; return false; }
+        xi[j] = std::log10(ki[j]);
+    }
+    DlSplineSetup spi;
+    if (!dl_spline_setup(xi, spi, err)) { err = w + "ws_k: " + err; return false; }
+    const double x0i = xi[0], inv_hi = (n_i - 1) / (xi[n_i - 1] - xi[0]);
+    for (int j = 0; j + 1 < n_i; ++j)   // uniform to rounding: the convolution assumes the Toeplitz system (dl_fs_phase2_fir)
+        if (std::fabs((xi[j + 1] - xi[j]) * inv_hi - 1.) > 1e-9) { err = w + "the inner grid ws_k must be uniform in log k (a slice of a geomspace)"; return false; }
+    std::vector<double> ctt, cnow;
+    double x0f, inv_hf, x0f2, inv_hf2;
+    if ((int)ptt.size() != n_f || (int)pnow.size() != n_f) { err = w + "ws_pk_tt_fid and ws_pknow_tt_fid must have one entry per wavenumber of ws_kfid"; return false; }
+    if (!dl_ws_loglog_polynomials(kf, ptt, w + "ws_kfid / ws_pk_tt_fid", ctt, x0f, inv_hf, err)) return false;
+    if (!dl_ws_loglog_polynomials(kf, pnow, w + "ws_kfid / ws_pknow_tt_fid", cnow, x0f2, inv_hf2, err)) return false;
+    // the reference slices its inner grid so that qbao cannot push it past the interpolator's bounds (power_template.py:1194); here the prior of qbao is [0.8, 1.2]
+    if (ki[0] / 1.2 < kf[0] || ki[n_i - 1] / 0.8 > kf[n_f - 1]) { err = w + "qbao in [0.8, 1.2] pushes the inner grid ws_k outside the fiducial table ws_kfid"; return false; }
+    if ((size_t)dl_ws_shared_doubles(n_i, DL_WS_THREADS) * sizeof(double) > 64 * 1024) { err = w + "inner grid too large for the 64 KiB LDS of the template kernel (about 3900 knots)"; return false; }
+    auto locate = [&](double k, double& interval, double& u) {   // false: the reference would be extrapolating its spline
+        const double t = (std::log10(k) - x0i) * inv_hi;
+        if (!(t >= -1e-9) || !(t <= (n_i - 1) + 1e-9)) return false;
+        int j = (int)(t > 0. ? t : 0.);
+        j = j > n_i - 2 ? n_i - 2 : j;
+        interval = (double)j; u = t - (double)j;
+        return true;
+    };
+    tab.assign((size_t)DL_WS_HEAD + 2 * (size_t)n_i + 8 * (size_t)(n_f - 1) + 4 * (size_t)n_q + 4 * (size_t)n_t, 0.);
+    tab[DL_WS_NI] = n_i; tab[DL_WS_NF] = n_f; tab[DL_WS_NQ_] = n_q; tab[DL_WS_NT] = n_t;
+    tab[DL_WS_X0F] = x0f; tab[DL_WS_INVHF] = inv_hf; tab[DL_WS_NORM] = (fsigmar / d.f_fid) * (fsigmar / d.f_fid);
+    tab[DL_WS_E0A] = spi.end0a; tab[DL_WS_E0B] = spi.end0b; tab[DL_WS_E1A] = spi.end1a; tab[DL_WS_E1B] = spi.end1b;
+    double* inner = tab.data() + DL_WS_HEAD;
+    double* fid = inner + 2 * (size_t)n_i;
+    double* quad = fid + 8 * (size_t)(n_f - 1);
+    double* knots = quad + 4 * (size_t)n_q;
+    for (int j = 0; j < n_i; ++j) { inner[2 * j] = xi[j]; inner[2 * j + 1] = pknow_i[j]; }
+    for (int j = 0; j < n_f - 1; ++j)
+        for (int q = 0; q < 4; ++q) { fid[8 * (size_t)j + q] = ctt[4 * (size_t)j + q]; fid[8 * (size_t)j + 4 + q] = cnow[4 * (size_t)j + q]; }
+    // integrate_sigma_r2 (power_template.py:1071-1076) AS WRITTEN: logk = linspace(log10 kmin, log10 kmax, nk), k = exp(logk), trapezoid in logk
+    const double lo = std::log10(1e-6), step = (std::log10(1e2) - lo) / (n_q - 1);
+    std::vector<double> logk(n_q);
+    for (int q = 0; q < n_q; ++q) logk[q] = q * step + lo;
+    logk[n_q - 1] = std::log10(1e2);
+    for (int q = 0; q < n_q; ++q) {
+        const double k = std::exp(logk[q]);
+        const double wq = 0.5 * ((q + 1 < n_q ? logk[q + 1] : logk[q]) - (q > 0 ? logk[q - 1] : logk[q]));
+        quad[4 * (size_t)q] = wq * dl_ws_kernel2(kernel, k * r) * (k * k * k) / (2. * M_PI * M_PI);
+        quad[4 * (size_t)q + 1] = std::log(k / kp);
+        if (!locate(k, quad[4 * (size_t)q + 2], quad[4 * (size_t)q + 3])) { err = w + "a node of the sigma_r quadrature (exp(-6) .. exp(2): 2.48e-3 .. 7.39) lies outside the inner grid ws_k: the reference would extrapolate"; return false; }
+    }
+    for (int j = 0; j < n_t; ++j) {
+        knots[4 * (size_t)j] = std::log(k_t[j] / kp);
+        if (!locate(k_t[j], knots[4 * (size_t)j + 1], knots[4 * (size_t)j + 2])) { err = w + "a template knot k_t lies outside the inner grid ws_k: the reference would extrapolate"; return false; }
+    }
+    return true;
 }
 
 // Cholesky factor of a symmetric positive-definite matrix: P = L L^T (lower), in place (upper part zeroed)
@@ -477,7 +600,11 @@ inline bool dl_build_obs(const dl_config& cfg, int iobs, int n_params, DlObsHost
         if (d.theory != 2) { err = p + "phase-shift template: BAO wiggle theories only (its parameter moves the wiggles, which only they evaluate apart)"; return false; }
         d.band_in[0] = dl_input_from(cfg, p + "in.baoshift", 1.);   // (dl_ps_baoshift: the band template's first slot)
         if (d.band_in[0].col >= n_params) { err = p + "in.baoshift: theta column out of range"; return false; }
-    } else if (d.templ < 0 || d.templ > 4) { err = p + "unknown template kind"; return false; }
+    } else if (d.templ == 5) {
+        if (d.theory != 0 && d.theory != 1) { err = p + "wiggle-split template: Kaiser / EFT-like Kaiser / Simple theories only"; return false; }
+        d.band_in[0] = dl_input_from(cfg, p + "in.qbao", 1.);   // (dl_ws_qbao: the band template's first slot)
+        if (d.band_in[0].col >= n_params) { err = p + "in.qbao: theta column out of range"; return false; }
+    } else if (d.templ < 0 || d.templ > 5) { err = p + "unknown template kind"; return false; }
     // template knots in log10 k (full_shape.py:498: interp1d(log10(kap), log10(k11), pk11))
     std::vector<double> x_t(d.n_t), sf_th(d.n_t), sf_lg(d.n_t), lkin(d.n_kin);
     for (int j = 0; j < d.n_t; ++j) {
@@ -716,7 +843,13 @@ inline bool dl_build_obs(const dl_config& cfg, int iobs, int n_params, DlObsHost
     oh.off_pass = arena.push(pass_tab);
     oh.off_png = arena.push(png_alpha);
     {
-        std::vector<double> band_tab = d.templ == 3 ? cfg.F(p + "band_templates") : d.templ == 4 ? ps_tab : std::vector<double>(2, 0.);   // (dl_ps_tab: the band template's pointer)
+        if (d.templ == 5) {   // wiggle-split template: constant tables (dl_wigglesplit.h); the scratch row the theory kernel copies is attached by the owner of the context
+            if (!dl_ws_build(cfg, p, d, k_t, oh.ws_tab, err)) return false;
+            oh.ws_qbao = d.band_in[0]; oh.ws_dm = d.dm;
+            d.pad_ml = (int32_t)oh.ws_tab[DL_WS_NI];   // (dl_ws_n_inner)
+            d.n_band = 0; d.coef_w = nullptr;          // (dl_ws_scratch_ld, dl_ws_scratch: set by whoever owns the scratch; the band loop of dl_fs_knots never runs for kind 5)
+        }
+        std::vector<double> band_tab = d.templ == 3 ? cfg.F(p + "band_templates") : d.templ == 4 ? ps_tab : d.templ == 5 ? oh.ws_tab : std::vector<double>(2, 0.);   // (dl_ps_tab, dl_ws_tab: the band template's pointer)
         oh.off_band = arena.push(band_tab);
     }
 

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "dl_fullshape.h"
+#include "dl_wigglesplit.h"
 #include <mutex>
 #include "dl_kernels.h"
 #include "dl_tns.h"
@@ -155,7 +156,7 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
         }
         if (mu_wave) dl_fs_mu_partA(o, th, mu_lane ? m : 0, c);
         else if (knot_rec) dl_fs_knots_rec(tid, KT, o, th, s, kr);
-        else dl_fs_knots(tid, KT, o, th, s);
+        else dl_fs_knots<!MOM>(tid, KT, o, th, s, b);   // (the moment form is the ShapeFit template's: the wiggle-split branch is not compiled into it)
         if (o.fixed_spline && mu_wave) {
             dl_fs_mu_partB(c);
             if (mu_lane) dl_fs_mu_partC(o, s, m, c, false);
@@ -181,7 +182,7 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
         }
         if (mu_prio) __builtin_amdgcn_s_setprio(0);
     } else {
-        dl_fs_phase01(tid, nthr, o, th, s);
+        dl_fs_phase01<true>(tid, nthr, o, th, s, b);
         __syncthreads();
         if (stop_after == 1) return;
         if (toep) {
@@ -425,6 +426,7 @@ bool dl_launch_fullshape_ens(const DlObsDev* obs_host, int n_obs, const DlObsDev
         const DlObsDev& oh = obs_host[i];
         const bool generic = !oh.uniform_knots || !(oh.toeplitz || oh.fixed_spline);
         if (oh.theory >= 2 || generic || oh.n_ct > 0 || oh.n_sn > 0 || (oh.n_ell <= 3) != nl3) return false;
+        if (oh.templ == 5) return false;   // wiggle-split template: its kernel reads the proposal from memory; the caller takes the general route
     }
     static const int64_t dense_min = getenv("DL_FS_DENSE_MIN") ? atoll(getenv("DL_FS_DENSE_MIN")) : 4096;
     const bool dense = B * n_obs > dense_min, mom = !dense && dl_fs_use_moments(obs_host, n_obs);
@@ -668,8 +670,39 @@ __global__ __launch_bounds__(DL_FS_THREADS) void dl_emulated_kernel(const DlObsD
                  feat ? feat + (size_t)b * feat_ld + o.feat_off : nullptr);
 }
 
+// ---- wiggle-split template (template kind 5, dl_wigglesplit.h): one workgroup per point evaluates the template at the knots into the point's scratch row ----------
+__global__ __launch_bounds__(DL_WS_THREADS) void dl_ws_template_kernel(const double* __restrict__ tab, const DlInput qbao_in, const DlInput dm_in, const double* __restrict__ theta,
+                                                                       int n_params, double* __restrict__ scratch, int64_t ld) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int tid = threadIdx.x;
+    const double* th = theta + (size_t)blockIdx.x * n_params;
+    const double qbao = dl_get(qbao_in, th), dm = dl_get(dm_in, th);
+    const DlWsTab t = dl_ws_open(tab);
+    const DlWsShared s = dl_ws_carve(lds, t.n_i, DL_WS_THREADS);
+    double carry = 0.;
+    for (int phase = 0; phase < DL_WS_PHASES; ++phase) {   // (uniform: every thread reaches every barrier)
+        dl_ws_point_phase(phase, tid, DL_WS_THREADS, qbao, dm, t, s, carry, scratch + (size_t)blockIdx.x * ld);
+        __syncthreads();
+    }
+}
+
+// the template kernels of a theory launch: one per DISTINCT template (observables that share one point at the same scratch rows), on the stream of the theory kernels
+static void dl_launch_ws_templates(const DlObsDev* obs_host, int n_obs, const double* theta, int n_params, int64_t B, hipStream_t stream) {
+    for (int i = 0; i < n_obs; ++i) {
+        if (obs_host[i].templ != 5) continue;
+        bool done = false;
+        for (int j = 0; j < i; ++j) done = done || (obs_host[j].templ == 5 && dl_ws_scratch(obs_host[j]) == dl_ws_scratch(obs_host[i]));
+        if (done) continue;
+        const size_t shm = dl_ws_shared_doubles(dl_ws_n_inner(obs_host[i]), DL_WS_THREADS) * sizeof(double);
+        if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)dl_ws_template_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        DL_LAUNCH(dl_ws_template_kernel, dim3((unsigned)B), dim3(DL_WS_THREADS), shm, stream, dl_ws_tab(obs_host[i]), dl_ws_qbao(obs_host[i]), obs_host[i].dm, theta, n_params,
+                  const_cast<double*>(dl_ws_scratch(obs_host[i])), dl_ws_scratch_ld(obs_host[i]));
+    }
+}
+
 void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* theta, int n_params, int64_t B, double* power, int64_t ld_power, double* tables,
                          int64_t ld_tables, hipStream_t stream, double* feat, int64_t feat_ld, int xcd_block, const DlObsDev* obs_dev, bool moments) {
+    dl_launch_ws_templates(obs_host, n_obs, theta, n_params, B, stream);   // (before any theory kernel, merged launch included: their knot phase copies the rows)
     static const int stop_after = getenv("DL_FS_STOP") ? atoi(getenv("DL_FS_STOP")) : 0;   // per-phase timing diagnostics
     // DL_FS_STAMPS=<file>: in-kernel timestamps of the launches with B >= 256 are appended to <file> as text (synchronises: diagnostics only)
     static const char* stamp_file = getenv("DL_FS_STAMPS");
@@ -1343,6 +1376,7 @@ __global__ __launch_bounds__(1024) void dl_step_kernel(const DlObsDev o, const d
 size_t dl_step_lds_bytes(const DlObsDev& oh, int64_t B, int N_pad) {
     const bool generic = !oh.uniform_knots || !(oh.toeplitz || oh.fixed_spline);
     if (oh.theory >= 2 || generic || oh.n_ct > 0 || oh.n_sn > 0 || oh.n_ell > 3 || oh.n_pass != 0 || oh.n_var != 0 || N_pad != 128) return 0;
+    if (oh.templ == 5) return 0;   // (wiggle-split template: a kernel of its own runs before the theory)
     if (B <= 0 || B > 1024 || B % 256 != 0) return 0;     // whole groups of 8 row blocks: 64 workgroups
     const size_t per_point = (dl_fs_shared_doubles_obs(oh, true) + 1) / 2 * 2;
     const size_t bytes = std::max<size_t>(4 * per_point * sizeof(double), DL_CG_LDS_BYTES);

@@ -66,6 +66,24 @@ class SyntheticFiducial(object):
         return self._pk(k, 0.)
 
 
+class LogLogSpline(object):
+    """Tabulated spectrum as a not-a-knot cubic spline in (log10 k, log10 P): the form of cosmoprimo's ``PowerSpectrumInterpolator1D`` that the wiggle-split template
+    evaluates (power_template.py:1196-1201), and what ``dl_create`` builds from the same tables (csrc/dl_host.hpp, ``dl_ws_loglog_polynomials``).  On its own wavenumbers it
+    returns the table itself."""
+
+    def __init__(self, k, pk):
+        from scipy import interpolate
+        self.k, self.pk = np.array(k, dtype='f8'), np.array(pk, dtype='f8')
+        self.extrap_kmin, self.extrap_kmax = float(self.k[0]), float(self.k[-1])
+        self._spline = interpolate.CubicSpline(np.log10(self.k), np.log10(self.pk), bc_type='not-a-knot', extrapolate=True)
+
+    def __call__(self, k, **kwargs):
+        k = np.asarray(k, dtype='f8')
+        if k.shape == self.k.shape and np.array_equal(k, self.k):
+            return self.pk.copy()
+        return 10.**self._spline(np.log10(k))
+
+
 class FiducialWarning(UserWarning):
     """The synthetic stand-in cosmology was used where the reference would have used a real one."""
 

@@ -138,6 +138,8 @@ class _BaseDampedBAOTracer(BaseCalculator):
         template = init.get('template', None)
         if template is None:
             template = self.init['template'] = BAOPowerSpectrumTemplate()
+        if getattr(template, '_kind', 0) == 5:
+            raise NotImplementedError('{}: its no-wiggle outputs (pknow_*) are not built; supported are the Kaiser / Simple / EFT-like Kaiser multipoles, not {}'.format(template.__class__.__name__, self.__class__.__name__))
         self.template = self._require(template)
         tk = template.init.get('k', None)
         knots = np.geomspace(min(self._klim[0], self.kin[0] / 2, tk[0] if tk is not None else 1.), max(self._klim[1], self.kin[-1] * 2, tk[0] if tk is not None else 0.), self._klim[2])

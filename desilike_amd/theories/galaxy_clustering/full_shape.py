@@ -100,6 +100,8 @@ class KaiserTracerPowerSpectrumMultipoles(BaseCalculator):
         if getattr(template, '_kind', 0) == 4:
             raise NotImplementedError('{} moves the BAO wiggles, which only the BAO wiggle theories evaluate apart from the smooth power: supported are the Damped / Simple / '
                                       'Resummed / Flexible BAOWigglesTracer power spectrum and correlation function multipoles, not {}'.format(template.__class__.__name__, self.__class__.__name__))
+        if getattr(template, '_kind', 0) == 5 and self._kind not in (0, 1):
+            raise NotImplementedError('{} is built for the Kaiser family (Kaiser / Simple / EFT-like Kaiser multipoles and their correlation functions), not {}'.format(template.__class__.__name__, self.__class__.__name__))
         self.template = self._require(template)
         # template knots with margin for the AP effect (full_shape.py:29)
         tk = template.init.get('k', None)
@@ -560,6 +562,8 @@ class _BaseVelocileptorsTracer(BaseCalculator):
         if getattr(init.get('template', None), '_kind', 0) == 4:
             raise NotImplementedError('BAOPhaseShiftPowerSpectrumTemplate is supported by the BAO wiggle theories (Damped / Simple / Resummed / Flexible BAOWigglesTracer multipoles) only, '
                                       'not by {}'.format(self.__class__.__name__))
+        if getattr(init.get('template', None), '_kind', 0) == 5:
+            raise NotImplementedError('WiggleSplitPowerSpectrumTemplate is built for the Kaiser family (Kaiser / Simple / EFT-like Kaiser multipoles) only, not for {}'.format(self.__class__.__name__))
         if self.pt is None:
             raise ValueError('provide pt=EmulatedCalculator(...): the perturbation-theory engines are external CPU codes (out of scope)')
         self.prior_basis = init.get('prior_basis', 'physical')

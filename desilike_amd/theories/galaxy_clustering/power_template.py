@@ -171,6 +171,116 @@ class ShapeFitPowerSpectrumTemplate(BasePowerSpectrumTemplate):
         return super(ShapeFitPowerSpectrumTemplate, self).initialize()
 
 
+def _sigma_kernel2(kernel, x):
+    """:math:`W^2(x)` of the normalisation integral: 'gauss' :math:`e^{-x^2}`, 'tophat' :math:`[3 (\\sin x - x \\cos x) / x^3]^2` with its series below 0.1 (power_template.py:973-1030)."""
+    x = np.asarray(x, dtype='f8')
+    if kernel == 'gauss': return np.exp(-x**2)
+    x2 = x**2
+    low = 1. + x2 * (-1.0 / 10.0 + x2 * (1.0 / 280.0 + x2 * (-1.0 / 15120.0 + x2 * (1.0 / 1330560.0 + x2 * (-1.0 / 172972800.0)))))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        high = 3. * (np.sin(x) - x * np.cos(x)) / x**3
+    return np.where(x < 0.1, low, high)**2
+
+
+def integrate_sigma_r2(r, pk, kernel='gauss', kmin=1e-6, kmax=1e2, nk=2048):
+    r""":math:`\sigma_r^2 = \int dk k^2 P(k) W^2(k r) / (2 \pi^2)` with the reference's quadrature AS WRITTEN (power_template.py:1071-1076): nodes
+    ``exp(linspace(log10 kmin, log10 kmax, nk))`` -- 2.48e-3 to 7.39 for the defaults -- and a trapezoid in that linspace variable."""
+    logk = np.linspace(np.log10(kmin), np.log10(kmax), nk)
+    k = np.exp(logk)
+    integrand = pk(k)
+    integrand *= _sigma_kernel2(kernel, k * r) * k**3
+    trapezoid = getattr(np, 'trapezoid', None) or np.trapz
+    return 1. / 2. / np.pi**2 * trapezoid(integrand, x=logk, axis=0)
+
+
+class WiggleSplitPowerSpectrumTemplate(BasePowerSpectrumTemplate):
+    r"""Wiggle-split template (power_template.py:1150-1214): the fiducial BAO wiggles moved by ``qbao``, the spectrum tilted by ``dm`` around :math:`k_p = 0.05` and
+    re-normalised so that :math:`f \sigma_r = df \, (f \sigma_r)^{fid}`,
+
+    .. math:: P_{\theta\theta}(k) \propto \left[P_{now}^{fid}(k) + w(k / q_{BAO})\right] (k / k_p)^{dm}, \qquad w = P_{\theta\theta}^{fid} - P_{now,\theta\theta}^{fid},
+
+    :math:`P_{dd} = P_{\theta\theta} / f^2`, ``f = f_fid df``, single Alcock-Paczynski parameter ``qap`` (``apmode`` is forced to 'qap').  The bracket is tabulated on the
+    reference's inner grid (``geomspace(*klim_wiggles, 2000)`` without its outer octaves) and splined in (log10 k, log10 P); the normalisation is the reference's own
+    2048-node integral (:func:`integrate_sigma_r2`).  All of this runs per point on the GPU (csrc/dl_wigglesplit.h), for the Kaiser family: Kaiser / Simple / EFT-like
+    Kaiser multipoles and their correlation functions.  BAO, TNS, PNG and emulated theories raise ``NotImplementedError``, as does ``only_now=True``; the no-wiggle
+    outputs ``pknow_*`` and the derived parameter ``r`` of the reference's parameter file are not mirrored.
+
+    The fiducial :math:`P_{\theta\theta}` is ``f_fid^2 pk_dd`` of the fiducial provider (linear theory) unless ``pk_tt_fid`` (and ``pknow_tt_fid``) are given on the
+    provider's own wavenumbers, as for :class:`BandVelocityPowerSpectrumTemplate`.  A :class:`TabulatedFiducial` is splined on its own table; a :class:`SyntheticFiducial`
+    is first tabulated on the 2000-point ``geomspace(*klim_wiggles, 2000)``.
+
+    Parameters
+    ----------
+    r : float, default=8.
+        Smoothing radius of the normalisation.
+    kernel : str, default='gauss'
+        'gauss' or 'tophat'.
+    with_now : str, default='peakaverage'
+        Bookkeeping only: the no-wiggle table comes from the fiducial provider.
+    klim_wiggles : tuple, default=None
+        Ends of the 2000-point grid, same meaning and default as for :class:`BAOPhaseShiftPowerSpectrumTemplate`.
+    """
+    _kind = 5  # DL_TEMPLATE_WIGGLESPLIT
+    _with_now_default = 'peakaverage'
+    _nk_wiggles = 2000   # power_template.py:1193
+    _kp = 0.05           # power_template.py:1192
+    _own_params = {'qbao': dict(value=1., prior=dict(limits=[0.8, 1.2]), ref=dict(limits=[0.99, 1.01]), delta=0.008, latex=r'q_{\mathrm{BAO}}'),
+                   'dm': dict(value=0., prior=dict(limits=[-3., 3.]), ref=dict(limits=[-0.01, 0.01]), delta=0.005, latex='dm'),
+                   **_DF}
+    _extra_inputs = {'qbao': 'qbao'}
+
+    @classmethod
+    def _default_params(cls, **kwargs):
+        # power_template.yaml:351-388: qbao, qap, df, dm
+        import copy
+        params = copy.deepcopy(cls._own_params)
+        params['qap'] = copy.deepcopy(_AP['qap'])
+        return {name: params[name] for name in ['qbao', 'qap', 'df', 'dm']}
+
+    def initialize(self):
+        if self._initialized:
+            return self
+        from ...fiducial import LogLogSpline
+        init = self.init
+        init['apmode'] = 'qap'                      # power_template.py:1182
+        if init.get('only_now', False):
+            raise NotImplementedError('WiggleSplitPowerSpectrumTemplate: only_now is not implemented')
+        self.r = float(init.get('r', 8.))
+        self.kernel = str(init.get('kernel', 'gauss'))
+        if self.kernel not in ('gauss', 'tophat'):
+            raise ValueError('Unknown kernel {}; should be one of ["tophat", "gauss"]'.format(self.kernel))
+        super(WiggleSplitPowerSpectrumTemplate, self).initialize()
+        try:
+            table = getattr(self.fiducial, 'k', None)
+            klim = init.get('klim_wiggles', None)
+            if klim is None: klim = (1e-5, 1e2) if table is None else (float(table[0]), float(table[-1]))
+            self.klim_wiggles = (float(klim[0]), float(klim[1]))
+            kfid = np.geomspace(self.klim_wiggles[0], self.klim_wiggles[1], self._nk_wiggles) if table is None else np.asarray(table, dtype='f8')
+            pk_tt, pknow_tt = init.get('pk_tt_fid', None), init.get('pknow_tt_fid', None)
+            if (pk_tt is not None or pknow_tt is not None) and table is None:
+                raise ValueError('pk_tt_fid / pknow_tt_fid are tables on the wavenumbers of a TabulatedFiducial')
+            pk_tt = self.f_fid**2 * np.asarray(self.fiducial.pk_dd(kfid), dtype='f8') if pk_tt is None else np.asarray(pk_tt, dtype='f8')
+            pknow_tt = self.f_fid**2 * np.asarray(self.fiducial.pknow_dd(kfid), dtype='f8') if pknow_tt is None else np.asarray(pknow_tt, dtype='f8')
+            if pk_tt.shape != kfid.shape or pknow_tt.shape != kfid.shape:
+                raise ValueError('pk_tt_fid / pknow_tt_fid must have one entry per wavenumber of the fiducial table')
+            self.k_fid, self.pk_tt_fid, self.pknow_tt_fid = kfid, pk_tt, pknow_tt
+            self.pk_tt_interpolator_fid, self.pknow_tt_interpolator_fid = LogLogSpline(kfid, pk_tt), LogLogSpline(kfid, pknow_tt)
+            k = np.geomspace(self.klim_wiggles[0], self.klim_wiggles[1], self._nk_wiggles)       # power_template.py:1193-1194
+            self.k_wiggles = k[(k > k[0] * 2.) & (k < k[-1] / 2.)]
+            self.pknow_tt_wiggles = self.pknow_tt_interpolator_fid(self.k_wiggles)
+            self.fsigmar_fid = float(integrate_sigma_r2(self.r, self.pk_tt_interpolator_fid, kernel=self.kernel)**0.5)   # power_template.py:1136
+        except Exception:
+            self._initialized = False   # (set by the base class: a second call must raise again, not return a template without its tables)
+            raise
+        return self
+
+    def _template_spec(self):
+        spec = super(WiggleSplitPowerSpectrumTemplate, self)._template_spec()
+        spec.update(ws_k=self.k_wiggles, ws_pknow=self.pknow_tt_wiggles, ws_kfid=self.k_fid, ws_pk_tt_fid=self.pk_tt_fid, ws_pknow_tt_fid=self.pknow_tt_fid,
+                    ws_r=[self.r], ws_kernel=np.array([{'gauss': 0, 'tophat': 1}[self.kernel]], dtype='i4'), ws_kp=[self._kp], ws_fsigmar_fid=[self.fsigmar_fid])
+        return spec
+
+
 def find_turn_over(k, pk):
     """Turn-over of a tabulated spectrum: vertex of the parabola through the three points around the maximum in (log10 k, log10 P) (the reference's estimate,
     power_template.py:1205-1220).  Returns the wavenumber; the power there is read off the spectrum itself."""

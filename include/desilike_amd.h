@@ -64,7 +64,19 @@ typedef struct dl_ctx dl_ctx;         /* opaque; owns all persistent device cons
                                    * f64[2] (clip bounds of the shifted wavenumber; default: the ends of ps_k).  "k_t" must be uniform in log10 k to rounding (geomspace, >= 128
                                    * knots): the per-point spline of the shifted wiggles is solved by a convolution.  dl_create refuses the kind on another theory, k_t that is
                                    * not uniform, and an inner grid that is not uniform in log10 k. */
-#define DL_THEORY_KAISER      0   /* full_shape.py:488-500, 545-550 */
+#define DL_TEMPLATE_WIGGLESPLIT 5 /* power_template.py:1150-1214 (wiggle-split: qbao, qap, df, dm): v = [P_now,tt_fid(k_i) + w(k_i / qbao)] (k_i / kp)^dm on the inner grid k_i, w =
+                                   * P_tt_fid - P_now,tt_fid; P = spline of v in (log10 k, log10 P); P_dd(k_t) = P(k_t) fsigmar_fid^2 / (f_fid^2 I), I the reference's 2048-node
+                                   * sigma_r integral of P (power_template.py:1038-1076, as written); f = f_fid df.  Kaiser-type theories (theory = 0, 1); apmode as given (the
+                                   * reference forces DL_APMODE_QAP).  A template kernel of its own runs before the theory kernel (csrc/dl_wigglesplit.h); observables with equal
+                                   * tables and inputs share one evaluation per point.  Keys: "in.qbao" f64[2] (theta column or -1, value; default 1), "in.dm"; "ws_k" f64[n_i]
+                                   * (inner grid, uniform in log k, >= 128 knots) and "ws_pknow" f64[n_i] (P_now,tt_fid on it); "ws_kfid" f64[n_f] (fiducial grid, uniform in log
+                                   * k) with "ws_pk_tt_fid" f64[n_f] and "ws_pknow_tt_fid" f64[n_f] (splined in (log10 k, log10 P) at create); "ws_r" (smoothing radius, default
+                                   * 8), "ws_kernel" i32 (0 gauss, 1 tophat), "ws_kp" (pivot, default 0.05), "ws_fsigmar_fid".  "pk_dd_fid" f64[n_t] is not used (any positive
+                                   * table).  dl_create refuses: an inner grid that is not uniform in log k or has fewer than 128 knots, a node of the quadrature (2.48e-3 ..
+                                   * 7.39) or a template knot outside the inner grid, an inner grid that qbao in [0.8, 1.2] pushes outside the fiducial grid, another theory.
+                                   * Any finite qbao indexes inside the tables (the abscissa is clamped); NaN qbao / dm give NaN multipoles and DL_STATUS_NAN_INPUT.  No
+                                   * analytic gradient / Jacobian (dl_eval_grad, dl_eval_fisher_analytic return 2), no in-kernel-proposal ensemble form (general route). */
+#define DL_THEORY_KAISER      0  /* full_shape.py:488-500, 545-550 */
 #define DL_THEORY_EFT_KAISER  1   /* + counter / stochastic terms full_shape.py:628-634 */
 #define DL_THEORY_BAO_DAMPED  2   /* damped BAO wiggles, 'standard' model bao.py:117-140 (+ broadband terms as pass-through columns, bao.py:495-534, 881-905) */
 #define DL_THEORY_EMULATED    3   /* emulated P_ell tables (Taylor / MLP engines, emulators/base.py) + velocileptors bias-table combination full_shape.py:1150-1190 */
@@ -150,7 +162,8 @@ int  dl_create(dl_ctx** out, int device, const dl_config* cfg);
 void dl_destroy(dl_ctx* ctx);
 const char* dl_last_error(const dl_ctx* ctx);
 
-/* integer properties: "n_params", "n_data", "n_obs", "n_in_total", "n_in_obs<i>", "n_out_obs<i>", "n_solved", "device" */
+/* integer properties: "n_params", "n_data", "n_obs", "n_in_total", "n_in_obs<i>", "n_out_obs<i>", "n_solved", "device", "ws_ld" (doubles per point of the
+ * wiggle-split template scratch: the knot counts of the DISTINCT templates of kind 5, 0 without one) */
 int64_t dl_info(const dl_ctx* ctx, const char* key);
 
 /* ---- evaluation ------------------------------------------------------------------------------*/

@@ -24,7 +24,7 @@ import ctypes
 import numpy as np
 
 # enumerations of include/desilike_amd.h
-DL_TEMPLATE_FIXED, DL_TEMPLATE_SHAPEFIT, DL_TEMPLATE_TURNOVER, DL_TEMPLATE_BANDS, DL_TEMPLATE_PHASESHIFT = 0, 1, 2, 3, 4
+DL_TEMPLATE_FIXED, DL_TEMPLATE_SHAPEFIT, DL_TEMPLATE_TURNOVER, DL_TEMPLATE_BANDS, DL_TEMPLATE_PHASESHIFT, DL_TEMPLATE_WIGGLESPLIT = 0, 1, 2, 3, 4, 5
 DL_THEORY_KAISER, DL_THEORY_EFT_KAISER, DL_THEORY_BAO_DAMPED, DL_THEORY_EMULATED, DL_THEORY_TNS, DL_THEORY_PNG = 0, 1, 2, 3, 4, 5
 DL_APMODE = {'qparqper': 0, 'qiso': 1, 'qap': 2, 'qisoqap': 3}
 
@@ -536,7 +536,10 @@ def extract_config(likelihood):
         phaseshift = template.__class__.__name__.startswith('BAOPhaseShift') and not getattr(template, 'only_now', False)      # power_template.py:442-496
         if phaseshift and not bao:
             raise NotImplementedError('BAOPhaseShiftPowerSpectrumTemplate: BAO wiggle theories are covered')
-        cfg[p + 'template'] = np.array([DL_TEMPLATE_PHASESHIFT if phaseshift else DL_TEMPLATE_BANDS if bands else DL_TEMPLATE_TURNOVER if turnover else DL_TEMPLATE_SHAPEFIT if shapefit and not bao else DL_TEMPLATE_FIXED], dtype='i4')
+        wigglesplit = template.__class__.__name__.startswith('WiggleSplit')      # power_template.py:1150-1214
+        if wigglesplit and (bao or tns or png or getattr(template, 'only_now', False)):
+            raise NotImplementedError('WiggleSplitPowerSpectrumTemplate: Kaiser / Simple / EFT-like Kaiser theories are covered, without only_now')
+        cfg[p + 'template'] = np.array([DL_TEMPLATE_WIGGLESPLIT if wigglesplit else DL_TEMPLATE_PHASESHIFT if phaseshift else DL_TEMPLATE_BANDS if bands else DL_TEMPLATE_TURNOVER if turnover else DL_TEMPLATE_SHAPEFIT if shapefit and not bao else DL_TEMPLATE_FIXED], dtype='i4')
         if phaseshift:
             # the constants of calculate (power_template.py:489-491): shift of each template knot per unit (baoshift - 1), the reference's own fiducial wiggles on its own
             # 2000-point grid between the interpolator's extrapolation bounds, which are also the clip bounds of the shifted wavenumber
@@ -546,6 +549,17 @@ def extract_config(likelihood):
             cfg[p + 'ps_kshift'] = template.phiinf / (1.0 + (template.kstar / kt)**template.epsilon) / template.fiducial.rs_drag
             cfg[p + 'ps_k'], cfg[p + 'ps_klim'] = kw, np.array([kw[0], kw[-1]], dtype='f8')
             cfg[p + 'ps_wiggles'] = np.asarray(interpolator(kw), dtype='f8') - np.asarray(template.pknow_dd_interpolator_fid(kw), dtype='f8')
+        if wigglesplit:
+            # the constants of calculate (power_template.py:1192-1200): its inner grid, the fiducial interpolators tabulated on their own wavenumbers (dl_create splines them
+            # again in (log10 k, log10 P), the form cosmoprimo evaluates them in), the no-wiggle spectrum on the inner grid, the normalisation and its kernel
+            pk_tt, pknow_tt = template.pk_tt_interpolator_fid, template.pknow_tt_interpolator_fid
+            kw = np.geomspace(template.pk_dd_interpolator_fid.extrap_kmin, template.pk_dd_interpolator_fid.extrap_kmax, 2000)
+            kw = kw[(kw > kw[0] * 2.) & (kw < kw[-1] / 2.)]
+            kfid = np.asarray(pk_tt.k, dtype='f8')
+            cfg[p + 'ws_k'], cfg[p + 'ws_pknow'] = kw, np.asarray(pknow_tt(kw), dtype='f8')
+            cfg[p + 'ws_kfid'], cfg[p + 'ws_pk_tt_fid'], cfg[p + 'ws_pknow_tt_fid'] = kfid, np.asarray(pk_tt(kfid), dtype='f8'), np.asarray(pknow_tt(kfid), dtype='f8')
+            cfg[p + 'ws_r'], cfg[p + 'ws_kp'], cfg[p + 'ws_fsigmar_fid'] = np.array([template.r], dtype='f8'), np.array([0.05], dtype='f8'), np.array([template.fsigmar_fid], dtype='f8')
+            cfg[p + 'ws_kernel'] = np.array([0 if 'gauss' in template.kernel.__name__ else 1], dtype='i4')
         if turnover: cfg[p + 'kto_fid'], cfg[p + 'pkto_fid'] = np.array([template.kTO_fid], dtype='f8'), np.array([template.pkTO_dd_fid], dtype='f8')
         cfg[p + 'apmode'] = np.array([_apmode(template)], dtype='i4')
         cfg[p + 'transform'] = np.array([1 if getattr(obs, 'transform', None) == 'cubic' else 0], dtype='i4')
@@ -665,6 +679,7 @@ def extract_config(likelihood):
         if bao: defaults.update(dbeta=1., sigmas=0.)
         else: defaults.update(sn0=0.)
         if phaseshift: defaults.update(baoshift=1.)
+        if wigglesplit: defaults.update(qbao=1.)
         if resummed: names.setdefault('dres', names.get('d', 'd')); defaults.update(dres=1.)      # (growth rescaling `d` of the resummed wiggles, bao.py:201: the key's name is dres)
         if xi and not bao: defaults.pop('sn0')                             # no stochastic parameter for correlation functions (full_shape.py:336-364)
         for key, default in defaults.items():

@@ -32,6 +32,9 @@ SYMBOLS = {
     'dl_eval_logposterior': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_logposterior_grad': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_fisher': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_data_set': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int32]),
+    'dl_eval_logposterior_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_eval_fisher_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_fisher_analytic': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_theory': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_batch_host': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_int32_p, _c_double_p]),
@@ -308,6 +311,20 @@ def fill_config(spec, set_f64, set_i32):
             put(key, value)
 
 
+def check_data_batch(flatdata, n_data):
+    """``flatdata`` as a contiguous float64 array ``[M, n_data]``; raises :class:`ValueError` for another shape, more than 65536 vectors or a NaN / infinite entry."""
+    flatdata = np.asarray(flatdata, dtype='f8')
+    if flatdata.ndim == 1 and flatdata.size == n_data: flatdata = flatdata[None, :]
+    if flatdata.ndim != 2 or flatdata.shape[1] != n_data:
+        raise ValueError('a data batch must have shape (M, {:d}), found {}'.format(n_data, flatdata.shape))
+    if flatdata.shape[0] > 65536:
+        raise ValueError('a data batch holds at most 65536 data vectors, found {:d}'.format(flatdata.shape[0]))
+    bad = np.flatnonzero(~np.isfinite(flatdata).all(axis=1))
+    if bad.size:
+        raise ValueError('data vector {:d} of the batch has a NaN or infinite entry'.format(bad[0]))
+    return np.ascontiguousarray(flatdata)
+
+
 class Context(_Handle):
     """Owner of one ``dl_ctx`` (device constants + workspaces) on one GPU."""
     _prefix = 'dl'
@@ -560,6 +577,72 @@ class Context(_Handle):
             assert tensor.is_contiguous() and tensor.dtype == torch.float64 and tuple(tensor.shape) == shape
         self._check(self._lib.dl_eval_fisher(self._handle, ctypes.c_void_p(centers.data_ptr()), ctypes.c_void_p(steps.data_ptr()), B, ctypes.c_void_p(hessian.data_ptr()),
                                              ctypes.c_void_p(gradient.data_ptr()), ctypes.c_void_p(offset.data_ptr()), ctypes.c_void_p(stream)))
+        return hessian, gradient, offset
+
+    # ---- data batch (dl_data_set; csrc/dl_data_batch.h): many data vectors against one context ----
+    def set_data_batch(self, flatdata):
+        """Give the context ``flatdata [M, n_data]`` (host array, rows in the order of the context's own data vector) as its data batch (``dl_data_set``); ``None`` or
+        an empty array frees it.  Shape and finiteness are checked here, before any device call."""
+        if flatdata is None: flatdata = np.empty((0, self.n_data), dtype='f8')
+        flatdata = check_data_batch(flatdata, self.n_data)
+        self._check(self._lib.dl_data_set(self._handle, _f64_ptr(flatdata), flatdata.shape[0]))
+        return flatdata.shape[0]
+
+    @property
+    def n_data_batch(self):
+        return self.info('n_data_batch')
+
+    def eval_logposterior_data(self, theta, index=None, out=None, status=None, stream=None):
+        """Log-posteriors against the data batch (``dl_eval_logposterior_data``): ``theta [B, P]`` float64 device tensor; ``index`` ``None`` -> ``out [B, M]`` (every
+        point against every data vector), else an int32 device tensor ``[B]`` -> ``out [B]`` (point b against data vector ``index[b]``).  Asynchronous."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(theta.device).cuda_stream
+        B = theta.shape[0]
+        theta = self._device_theta(theta, stream)
+        shape = (B, self.n_data_batch) if index is None else (B,)
+        if index is not None: assert index.is_contiguous() and index.dtype == torch.int32 and tuple(index.shape) == (B,)
+        if out is None: out = torch.empty(shape, dtype=torch.float64, device=theta.device)
+        assert out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == shape
+        assert status is None or (status.is_contiguous() and status.dtype == torch.int32 and tuple(status.shape) == (B,))
+        self._check(self._lib.dl_eval_logposterior_data(self._handle, ctypes.c_void_p(theta.data_ptr()), B, None if index is None else ctypes.c_void_p(index.data_ptr()),
+                                                        ctypes.c_void_p(out.data_ptr()), None if status is None else ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(stream)))
+        return out
+
+    def eval_logposterior_data_host(self, theta, index=None):
+        """numpy in / numpy out: (logposterior [B, M] or [B], status [B]); stages through device tensors."""
+        import torch
+        theta = np.ascontiguousarray(np.atleast_2d(theta), dtype='f8')
+        device = torch.device('cuda', self.device)
+        th = torch.as_tensor(theta, dtype=torch.float64, device=device).contiguous()
+        if index is not None:
+            index = np.ascontiguousarray(index, dtype='i4')
+            if index.shape != (theta.shape[0],): raise ValueError('index must have shape ({:d},), found {}'.format(theta.shape[0], index.shape))
+            index = torch.as_tensor(index, device=device)
+        status = torch.zeros(theta.shape[0], dtype=torch.int32, device=device)
+        out = self.eval_logposterior_data(th, index=index, status=status)
+        torch.cuda.synchronize(device)
+        return out.cpu().numpy(), status.cpu().numpy()
+
+    def eval_fisher_data(self, centers, steps, index, hessian=None, gradient=None, offset=None, stream=None):
+        """:meth:`eval_fisher` with the residual of centre b taken against data vector ``index[b]`` of the data batch (``dl_eval_fisher_data``; ``index`` int32 device
+        tensor ``[B]``)."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(centers.device).cuda_stream
+        B, P = centers.shape
+        if self.expand is not None:
+            raise NotImplementedError('Fisher algebra with parameters derived by an expression: differentiate w.r.t. the device columns and apply the chain rule on the host')
+        assert P == self.n_params and centers.is_contiguous() and centers.dtype == torch.float64
+        assert steps.is_contiguous() and steps.dtype == torch.float64 and tuple(steps.shape) == (B, P, 2)
+        assert index.is_contiguous() and index.dtype == torch.int32 and tuple(index.shape) == (B,)
+        if hessian is None: hessian = torch.empty((B, P, P), dtype=torch.float64, device=centers.device)
+        if gradient is None: gradient = torch.empty((B, P), dtype=torch.float64, device=centers.device)
+        if offset is None: offset = torch.empty(B, dtype=torch.float64, device=centers.device)
+        for tensor, shape in [(hessian, (B, P, P)), (gradient, (B, P)), (offset, (B,))]:
+            assert tensor.is_contiguous() and tensor.dtype == torch.float64 and tuple(tensor.shape) == shape
+        self._check(self._lib.dl_eval_fisher_data(self._handle, ctypes.c_void_p(centers.data_ptr()), ctypes.c_void_p(steps.data_ptr()), B, ctypes.c_void_p(index.data_ptr()),
+                                                  ctypes.c_void_p(hessian.data_ptr()), ctypes.c_void_p(gradient.data_ptr()), ctypes.c_void_p(offset.data_ptr()), ctypes.c_void_p(stream)))
         return hessian, gradient, offset
 
     def eval_fisher_analytic(self, centers, hessian=None, gradient=None, offset=None, stream=None):

@@ -4,6 +4,7 @@
 #include <thread>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -15,9 +16,36 @@
 #include "dl_ens_fold.h"
 #include "dl_prior.h"
 #include "dl_sample_solved.h"
+#include "dl_data_batch.h"
 
 static thread_local std::string g_last_error;
 void dl_set_last_error(const char* msg) { g_last_error = msg ? msg : ""; }
+
+// The additive term of the whitened residual for one data vector: row i of L^T X = sum_j L[j][i] X[j] over the non-zero entries of column i of the factor, j increasing
+// (a Cholesky factor: j >= i; a dense factor given by the host: every j).  dl_create uses it for the context's own data vector, dl_data_set for every vector of a
+// data batch: one arithmetic for both.
+struct DlWhitenHost {
+    int n = 0;
+    std::vector<int64_t> col_ptr;    // [n + 1]
+    std::vector<int> row;            // j of every non-zero L[j][i], column after column
+    std::vector<double> val;         // L[j][i]
+    std::vector<int> white_row;      // [n] position of whitened row i in the residual layout
+    std::vector<double> bias_full;   // [n] additive term of the window (flattheory = W . power + bias_full)
+    // flatdata [n] -> bias_white [N_pad] (entries at white_row: L^T (bias_full - flatdata)), bias_wh [N_pad] (-L^T flatdata; may be null); other entries are left alone
+    void apply(const double* flatdata, double* bias_white, double* bias_wh) const {
+        for (int i = 0; i < n; ++i) {
+            double bsum = 0., dsum = 0.;
+            for (int64_t e = col_ptr[i]; e < col_ptr[i + 1]; ++e) {
+                const int j = row[e];
+                const double lji = val[e];
+                bsum += lji * (bias_full[j] - flatdata[j]);
+                dsum += lji * flatdata[j];
+            }
+            bias_white[white_row[i]] = bsum;
+            if (bias_wh) bias_wh[white_row[i]] = -dsum;
+        }
+    }
+};
 
 struct dl_ctx {
     int device = 0;
@@ -98,6 +126,12 @@ struct dl_ctx {
     double *ss_solved = nullptr, *ss_hessian = nullptr, *ss_loglike = nullptr, *ss_logprior = nullptr;
     int32_t* ss_status = nullptr;
     int64_t ss_cap = 0;
+    // data batch (dl_data_set, dl_data_batch.h): what the whitening of a data vector needs on the host -- the non-zero entries of the factor L column by column
+    // (column i: rows j in increasing order), the position of every whitened row, the additive term of the window -- and the table of whitened biases [M, N_pad]
+    DlWhitenHost whiten;
+    int n_data_batch = 0;
+    double* data_bias_dev = nullptr;
+    int32_t* data_index_ws = nullptr;   // [DL_CHUNK] checked data indices of the centres of a pass of dl_eval_fisher_data
     // the workspaces are shared by every call on this context: a call on another stream than the previous one waits for it (event recorded on the old stream
     // at the moment of the switch: calls that stay on one stream pay nothing)
     hipStream_t last_stream = nullptr;
@@ -301,21 +335,25 @@ int dl_create(dl_ctx** out, int device, const dl_config* cfg) {
         }
     }
     // whitened: row i of (L^T . X) = sum_{j >= i} L[j][i] X[j]
+    DlWhitenHost& whiten = ctx->whiten;
+    whiten.n = n;
+    whiten.white_row = wr;
+    whiten.bias_full.assign(bias_full.begin(), bias_full.begin() + n);
+    whiten.col_ptr.assign(1, 0);
     for (int i = 0; i < n; ++i) {
         double* dst = &wt_white[(size_t)wr[i] * ctx->K_pad];
-        double bsum = 0., dsum = 0.;
         for (int j = dense_factor ? 0 : i; j < n; ++j) {
             double lji = L[(size_t)j * n + i];
             if (lji == 0.) continue;
             const double* src = &wt_full[(size_t)j * ctx->K_pad];
             for (int k = 0; k < K; ++k) dst[k] += lji * src[k];
-            bsum += lji * (bias_full[j] - flatdata[j]);
-            dsum += lji * flatdata[j];
             wh[(size_t)wr[i] * ctx->N_pad + j] = lji;
+            whiten.row.push_back(j);
+            whiten.val.push_back(lji);
         }
-        bias_white[wr[i]] = bsum;
-        bias_wh[wr[i]] = -dsum;
+        whiten.col_ptr.push_back((int64_t)whiten.row.size());
     }
+    whiten.apply(flatdata.data(), bias_white.data(), bias_wh.data());   // (the additive terms: the arithmetic dl_data_set repeats for every vector of a data batch)
     // ---- non-zero K panels per 16-row block of the whitened operator (block-diagonal precisions leave whole panels zero) ----
     if (ctx->K_pad / 128 <= 255 && !getenv("DL_NO_PANEL_SKIP")) {
         const int n_tiles = ctx->N_pad / 16, n_panels = ctx->K_pad / 128;
@@ -518,6 +556,8 @@ void dl_destroy(dl_ctx* ctx) {
     if (ctx->grad_status) (void)hipFree(ctx->grad_status);
     for (double* p : {ctx->ss_solved, ctx->ss_hessian, ctx->ss_loglike, ctx->ss_logprior}) if (p) (void)hipFree(p);
     if (ctx->ss_status) (void)hipFree(ctx->ss_status);
+    if (ctx->data_bias_dev) (void)hipFree(ctx->data_bias_dev);
+    if (ctx->data_index_ws) (void)hipFree(ctx->data_index_ws);
     void* ptrs[] = {ctx->arena_dev, ctx->priors_dev, ctx->wt_white_dev, ctx->wt_frag_dev, ctx->bias_white_dev, ctx->wt_full_dev, ctx->bias_full_dev, ctx->wh_dev,
                     ctx->bias_wh_dev, ctx->flatdata_dev, ctx->transform_dev, ctx->tconst_dev, ctx->power_ws, ctx->delta_ws, ctx->flat_ws, ctx->stencil_ws, ctx->theta_stage, ctx->out_stage,
                     ctx->status_stage, ctx->gemm_counters, ctx->obs_array_dev, ctx->ws_scratch};
@@ -548,6 +588,7 @@ int64_t dl_info(const dl_ctx* ctx, const char* key) {
     if (k == "K_pad") return ctx->K_pad;
     if (k == "N_pad") return ctx->N_pad;
     if (k == "n_solved") return ctx->n_solved;
+    if (k == "n_data_batch") return ctx->n_data_batch;
     if (k == "device") return ctx->device;
     if (k == "ws_ld") return ctx->ws_ld;   // doubles per point of the wiggle-split template scratch: the knot counts (rounded up to even) of the DISTINCT templates
     for (int i = 0; i < ctx->n_obs; ++i) {
@@ -602,8 +643,16 @@ static int dl_reserve(dl_ctx* ctx, int64_t B) {
     return 0;
 }
 
+// `data` of dl_eval_impl (dl_eval_logposterior_data): the pass stops after the GEMM of the RESIDUAL route -- theory kernels or the feature path, then the tiled split-K
+// window GEMM or the feature GEMM, un-biased rows in delta_ws; never the chi2 GEMMs, the fused step or a kernel with the finalize in its tail -- and the finalize of
+// the data batch (dl_data_batch.h) takes the place of the context's own.  Null (every other entry point): nothing changes.
+struct DlDataEval {
+    const int32_t* index;   // [B] device, or null: every data vector (out [B, M])
+    double* out;
+};
+
 static int dl_eval_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, double* loglike_dev, double* logprior_dev, double* flattheory_dev, int32_t* status_dev,
-                        double* solved_dev, void* hip_stream, int post_mode, double* hessian_dev = nullptr) {
+                        double* solved_dev, void* hip_stream, int post_mode, double* hessian_dev = nullptr, const DlDataEval* data = nullptr) {
     if (!ctx) { g_last_error = "dl_eval_batch: null context"; return 1; }
     if (B < 0 || (B > 0 && !theta_dev)) return dl_fail(ctx, "dl_eval_batch: invalid batch");
     if (B == 0) return 0;
@@ -634,7 +683,7 @@ static int dl_eval_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, double*
         const bool emu_fused_env = !dl_options().no_emu_fused;   // DL_NO_EMU_FUSED=1: theory kernel -> point records in HBM -> feature GEMM (two launches)
         const bool emu_fused = emu_fused_env || ctx->any_stacked;         // (a stacked table engine has the one-launch form only)
         const int64_t chi2_max_rows = dl_options().chi2_max_rows;   // above: split-K slabs + finalize win (measured: 4096 rows 40 vs 49 us; 1024 rows 18 vs 13 us)
-        const bool chi2_path = !feat_path && !ctx->any_transform && ctx->n_solved == 0 && nb <= chi2_max_rows;
+        const bool chi2_path = !data && !feat_path && !ctx->any_transform && ctx->n_solved == 0 && nb <= chi2_max_rows;
         // the chi2 GEMM consumes row block mb (32 points; the LDS-DMA GEMM: 64) on XCD mb % 8: have the theory kernel produce it there (power then waits in that XCD's L2:
         // -0.5 us per 1024 points)
         const int xcd_local = dl_options().xcd_local;   // 0: off, 1: chi2 GEMM path, 2: also the large-batch GEMM
@@ -678,7 +727,7 @@ static int dl_eval_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, double*
         bool gram_done = false, finalized_in_kernel = false, stacked_rows_done = false;
         const bool gram_epilogue = !dl_options().no_gram_epilogue;
         // (also without solved parameters: X is the residual row alone, chi2 = G[0][0] and the finalize -- priors, status -- runs in the kernel's tail: one launch instead of two)
-        if (feat_path && emu_fused && gram_epilogue && ctx->n_obs == 1 && ctx->N_pad == 128) {
+        if (!data && feat_path && emu_fused && gram_epilogue && ctx->n_obs == 1 && ctx->N_pad == 128) {
             DlGramFinalize fin = {ctx->priors_dev, loglike_dev ? loglike_dev + b0 : nullptr, logprior_dev ? logprior_dev + b0 : nullptr, status_dev ? status_dev + b0 : nullptr,
                                   solved_dev ? solved_dev + (size_t)b0 * ctx->n_solved : nullptr, hessian_dev ? hessian_dev + (size_t)b0 * ctx->n_solved * ctx->n_solved : nullptr,
                                   post_mode, false};
@@ -707,7 +756,7 @@ static int dl_eval_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, double*
         // larger plain batches: the LDS-DMA split-K GEMM with the same partial-chi2 epilogue (no residual slab is written or read)
         int cps_probe = 0;
         const bool chi2_big_allowed = !dl_options().no_chi2_big;
-        const bool chi2_big = !feat_path && !ctx->any_transform && ctx->n_solved == 0 && !chi2_path && ctx->K_pad % 32 == 0 && chi2_big_allowed &&
+        const bool chi2_big = !data && !feat_path && !ctx->any_transform && ctx->n_solved == 0 && !chi2_path && ctx->K_pad % 32 == 0 && chi2_big_allowed &&
                               dl_gemm_tiled_splits(nb, ctx->N_pad, ctx->K_pad, &cps_probe) == 1;   // enough row tiles to fill the chip without splitting K
         int part_tiles = ctx->N_pad / 16;
         // DL_CHI2_FUSED=1: finalize inside the GEMM's last-arriving workgroups.  Off by default: measured 19.1 us (GEMM 17.1) against 17.5 us for GEMM + the
@@ -738,7 +787,11 @@ static int dl_eval_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, double*
                                         stream, ctx->n_white);
         }
         prof_phase(2);
-        if (chi2_path && chi2_fused) {
+        if (data)
+            dl_launch_data_finalize(ctx->delta_ws, ctx->N_pad, ctx->n_white, n_slabs, slab_stride, ctx->data_bias_dev, ctx->N_pad, ctx->n_data_batch,
+                                    data->index ? data->index + b0 : nullptr, th, P, ctx->priors_dev, nb, data->out + (size_t)b0 * (data->index ? 1 : ctx->n_data_batch),
+                                    status_dev ? status_dev + b0 : nullptr, stream);
+        else if (chi2_path && chi2_fused) {
             // finalize fused into the GEMM
         } else if (finalized_in_kernel) {
             // marginalised finalize in the tail of the fused emulator / feature-GEMM kernel
@@ -818,7 +871,9 @@ int dl_eval_logposterior(dl_ctx* ctx, const double* theta_dev, int64_t B, double
     return dl_eval_impl(ctx, theta_dev, B, logposterior_dev, nullptr, nullptr, status_dev, nullptr, hip_stream, 1);
 }
 
-int dl_eval_fisher(dl_ctx* ctx, const double* centers_dev, const double* steps_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, void* hip_stream) {
+// data_index_dev (dl_eval_fisher_data): residual row 0 of centre b against vector data_index[b] of the data batch; null: the launches of dl_eval_fisher
+static int dl_eval_fisher_impl(dl_ctx* ctx, const double* centers_dev, const double* steps_dev, int64_t B, const int32_t* data_index_dev, double* hessian_dev, double* gradient_dev,
+                               double* offset_dev, void* hip_stream) {
     if (!ctx) { g_last_error = "dl_eval_fisher: null context"; return 1; }
     if (B < 0 || (B > 0 && (!centers_dev || !steps_dev))) return dl_fail(ctx, "dl_eval_fisher: invalid argument");
     if (ctx->n_solved > 0) return dl_fail(ctx, "dl_eval_fisher: the context has analytically solved parameters: create it with these parameters varied (the reference does the same, fisher.py:688-695)");
@@ -866,11 +921,63 @@ int dl_eval_fisher(dl_ctx* ctx, const double* centers_dev, const double* steps_d
                 dl_launch_window_gemm_tiled(ctx->power_ws, ctx->K_pad, ctx->wt_white_dev, ctx->K_pad, ctx->delta_ws, slab_stride, ctx->N_pad, nb, ctx->N_pad, ctx->K_pad, n_slabs, cps, stream, ctx->n_white);
             }
         }
+        if (data_index_dev) {
+            dl_launch_data_index(data_index_dev + b0, nc, ctx->n_data_batch, ctx->data_index_ws, stream);
+            dl_launch_fisher(ctx->delta_ws, ctx->N_pad, ctx->n_white, n_slabs, slab_stride, ctx->data_bias_dev, steps, P, nc, hessian_dev ? hessian_dev + (size_t)b0 * P * P : nullptr,
+                             gradient_dev ? gradient_dev + (size_t)b0 * P : nullptr, offset_dev ? offset_dev + b0 : nullptr, stream, ctx->data_index_ws, ctx->N_pad);
+        } else
         dl_launch_fisher(ctx->delta_ws, ctx->N_pad, ctx->n_white, n_slabs, slab_stride, bias, steps, P, nc, hessian_dev ? hessian_dev + (size_t)b0 * P * P : nullptr,
                          gradient_dev ? gradient_dev + (size_t)b0 * P : nullptr, offset_dev ? offset_dev + b0 : nullptr, stream);
     }
     DL_HIP_CHECK(ctx, hipGetLastError());
     return 0;
+}
+
+int dl_eval_fisher(dl_ctx* ctx, const double* centers_dev, const double* steps_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, void* hip_stream) {
+    return dl_eval_fisher_impl(ctx, centers_dev, steps_dev, B, nullptr, hessian_dev, gradient_dev, offset_dev, hip_stream);
+}
+
+int dl_eval_fisher_data(dl_ctx* ctx, const double* centers_dev, const double* steps_dev, int64_t B, const int32_t* data_index_dev, double* hessian_dev, double* gradient_dev,
+                        double* offset_dev, void* hip_stream) {
+    if (!ctx) { g_last_error = "dl_eval_fisher_data: null context"; return 1; }
+    if (ctx->n_data_batch == 0) return dl_fail(ctx, "dl_eval_fisher_data: the context has no data batch (dl_data_set)");
+    if (B > 0 && !data_index_dev) return dl_fail(ctx, "dl_eval_fisher_data: null data index");
+    return dl_eval_fisher_impl(ctx, centers_dev, steps_dev, B, data_index_dev, hessian_dev, gradient_dev, offset_dev, hip_stream);
+}
+
+// Data batch: M data vectors next to the context's own (dl_data_batch.h).  Host arithmetic of dl_create (DlWhitenHost::apply), one row of [M, N_pad] per vector.
+int dl_data_set(dl_ctx* ctx, const double* flatdata, int32_t M) {
+    if (!ctx) { g_last_error = "dl_data_set: null context"; return 1; }
+    if (M < 0 || M > DL_DB_MAX_M) return dl_fail(ctx, "dl_data_set: the number of data vectors must lie in [0, 65536]");
+    if (M > 0 && !flatdata) return dl_fail(ctx, "dl_data_set: null data");
+    if (ctx->any_transform) return dl_fail(ctx, "dl_data_set: the context has an observable transform: its residual is not additive in the data");
+    if (ctx->n_solved > 0) return dl_fail(ctx, "dl_data_set: the context has analytically solved parameters: create it with these parameters varied, or with the marginalised precision");
+    const int n = ctx->n_data;
+    for (int64_t e = 0; e < (int64_t)M * n; ++e)
+        if (!std::isfinite(flatdata[e])) return dl_fail(ctx, "dl_data_set: data vector " + std::to_string(e / n) + " has a NaN or infinite entry");
+    DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    DL_HIP_CHECK(ctx, hipDeviceSynchronize());   // kernels of earlier calls (any stream) may still read the table about to be replaced
+    if (ctx->data_bias_dev) { (void)hipFree(ctx->data_bias_dev); ctx->data_bias_dev = nullptr; }
+    ctx->n_data_batch = 0;
+    if (M == 0) {
+        if (ctx->data_index_ws) { (void)hipFree(ctx->data_index_ws); ctx->data_index_ws = nullptr; }
+        return 0;
+    }
+    std::vector<double> table((size_t)M * ctx->N_pad, 0.);
+    for (int32_t m = 0; m < M; ++m) ctx->whiten.apply(flatdata + (size_t)m * n, &table[(size_t)m * ctx->N_pad], nullptr);
+    if (dl_upload(ctx, &ctx->data_bias_dev, table)) return 1;
+    if (!ctx->data_index_ws) DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->data_index_ws, (size_t)DL_CHUNK * sizeof(int32_t)));
+    DL_HIP_CHECK(ctx, hipDeviceSynchronize());
+    ctx->n_data_batch = M;
+    return 0;
+}
+
+int dl_eval_logposterior_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, double* out_dev, int32_t* status_dev, void* hip_stream) {
+    if (!ctx) { g_last_error = "dl_eval_logposterior_data: null context"; return 1; }
+    if (ctx->n_data_batch == 0) return dl_fail(ctx, "dl_eval_logposterior_data: the context has no data batch (dl_data_set)");
+    if (B > 0 && !out_dev) return dl_fail(ctx, "dl_eval_logposterior_data: null output");
+    const DlDataEval data = {data_index_dev, out_dev};
+    return dl_eval_impl(ctx, theta_dev, B, nullptr, nullptr, nullptr, status_dev, nullptr, hip_stream, 1, nullptr, &data);
 }
 
 // Fisher algebra from EXACT derivative rows (dl_fullshape_jac.h).  Per pass: theory -> chi2 GEMM with the residual output (d~; its partial chi2 are not used) -> Jacobian

@@ -37,7 +37,11 @@ void dl_launch_fisher_stencil(const double* centers, const double* steps, int P,
 // TILES = ceil((P + 1) / 16): 16 x 16 tiles of the Gram matrix per side (1 or 2).  One wavefront per centre, WAVES of them per workgroup.
 // GIVEN: the rows already ARE derivatives (dl_eval_fisher_analytic): row (b, p) of `rows` = D~_p of centre b (the slabs of the window GEMM of the Jacobian rows, no bias),
 // d~ = row b of `resid` (bias included); nothing is differenced and `steps` / `bias` are not read.
-template <int TILES, bool GIVEN = false>
+// DATA (dl_eval_fisher_data; not with GIVEN): `bias` is a table of whitened bias rows, one per data vector, and residual row 0 of centre b takes row data_index[b] of it.
+// The kernel's argument list is that of the other instantiations, which stay as they are: the two arguments GIVEN alone reads carry the checked indices
+// (`resid`, read as int32 [B]: -1 for an index outside the table, dl_data_batch.h) and the stride of the table (`ldr`).  Row 0 of a centre without a valid index is
+// NaN (offset and gradient NaN, the Hessian does not depend on the data).
+template <int TILES, bool GIVEN = false, bool DATA = false>
 __global__ __launch_bounds__(256) void dl_fisher_kernel(const double* __restrict__ rows, int64_t ld, int n, int n_slabs, int64_t slab_stride, const double* __restrict__ bias,
                                                         const double* __restrict__ steps, int P, int64_t B, int waves, int chunk, double* __restrict__ hessian,
                                                         double* __restrict__ gradient, double* __restrict__ offset, const double* __restrict__ resid = nullptr, int64_t ldr = 0) {
@@ -51,6 +55,7 @@ __global__ __launch_bounds__(256) void dl_fisher_kernel(const double* __restrict
     double* X = dl_fi_lds + (size_t)wave * (TILES * 16) * stride;
     const double* row0 = rows + (size_t)b * (GIVEN ? P : S) * ld;
     const int xr = lane & 15, g = lane >> 4;
+    const int data_row = DATA ? reinterpret_cast<const int32_t*>(resid)[b] : 0;
     dl_fi_double4 acc[TILES][TILES];
 #pragma unroll
     for (int i = 0; i < TILES; ++i)
@@ -70,7 +75,10 @@ __global__ __launch_bounds__(256) void dl_fisher_kernel(const double* __restrict
                     for (int sl = 0; sl < n_slabs; ++sl) v += *reinterpret_cast<const dl_fi_double2*>(dr + (size_t)sl * slab_stride + c0);
                 }
             } else if (r == 0) {
-                if (bias) v = *reinterpret_cast<const dl_fi_double2*>(bias + c0);
+                if (DATA) {
+                    if (data_row >= 0) v = *reinterpret_cast<const dl_fi_double2*>(bias + (size_t)data_row * ldr + c0);
+                    else v = dl_fi_double2{__builtin_nan(""), __builtin_nan("")};
+                } else if (bias) v = *reinterpret_cast<const dl_fi_double2*>(bias + c0);
                 for (int sl = 0; sl < n_slabs; ++sl) v += *reinterpret_cast<const dl_fi_double2*>(row0 + (size_t)sl * slab_stride + c0);
             } else if (r < nrows) {
                 const int p = r - 1;
@@ -141,16 +149,20 @@ int dl_fisher_waves(int n, int P, size_t* shm_bytes, int* chunk_out) {
 }
 
 void dl_launch_fisher(const double* rows, int64_t ld, int n, int n_slabs, int64_t slab_stride, const double* bias, const double* steps, int P, int64_t B, double* hessian,
-                      double* gradient, double* offset, hipStream_t stream) {
+                      double* gradient, double* offset, hipStream_t stream, const int32_t* data_index, int64_t ldb) {
     size_t shm = 0;
     int chunk = 0;
     const int waves = dl_fisher_waves(n, P, &shm, &chunk);
     const unsigned grid = (unsigned)((B + waves - 1) / waves);
     auto launch = [&](auto kernel) {
         if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        DL_LAUNCH(kernel, dim3(grid), dim3(64 * waves), shm, stream, rows, ld, n, n_slabs, slab_stride, bias, steps, P, B, waves, chunk, hessian, gradient, offset, (const double*)nullptr, (int64_t)0);
+        DL_LAUNCH(kernel, dim3(grid), dim3(64 * waves), shm, stream, rows, ld, n, n_slabs, slab_stride, bias, steps, P, B, waves, chunk, hessian, gradient, offset,
+                  reinterpret_cast<const double*>(data_index), data_index ? ldb : (int64_t)0);
     };
-    if (P + 1 <= 16) launch(dl_fisher_kernel<1>);
+    if (data_index) {   // per-centre data vector: `bias` is the table [M, ldb], data_index the CHECKED indices (-1: none)
+        if (P + 1 <= 16) launch(dl_fisher_kernel<1, false, true>);
+        else launch(dl_fisher_kernel<2, false, true>);
+    } else if (P + 1 <= 16) launch(dl_fisher_kernel<1>);
     else launch(dl_fisher_kernel<2>);
 }
 

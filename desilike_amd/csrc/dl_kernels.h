@@ -129,7 +129,8 @@ bool dl_launch_emulated_feature_gram(const DlObsDev& obs, const double* theta, i
 void dl_launch_fisher_stencil(const double* centers, const double* steps, int P, int64_t B, double* theta, hipStream_t stream);
 int dl_fisher_waves(int n, int P, size_t* shm_bytes, int* chunk);   // centres per workgroup and columns staged at a time (0: no chunk fits the LDS)
 void dl_launch_fisher(const double* rows, int64_t ld, int n, int n_slabs, int64_t slab_stride, const double* bias, const double* steps, int P, int64_t B, double* hessian,
-                      double* gradient, double* offset, hipStream_t stream);
+                      double* gradient, double* offset, hipStream_t stream,
+                      const int32_t* data_index = nullptr, int64_t ldb = 0);   // data_index [B] (checked: -1 or a row of the table): `bias` is a table [M, ldb] of whitened bias rows (dl_data_batch.h)
 // Internal (dl_api.hip -> dl_ensemble.hip): theory + chi2 GEMM of B <= 2048 points of a plain likelihood, WITHOUT the finalize launch: *part = partial chi2
 // [B, *n_tiles] (the context's workspace: valid until its next call), *priors = the prior table [P, 5].  Returns 0, 1 (error) or 2 (this context / batch does not
 // take the chi2 GEMM path: use dl_eval_logposterior).

@@ -102,6 +102,25 @@ class Fisher(object):
         self.varied_params = ParameterCollection(list(likelihood.varied_params) + solved)
         self._solved_names = [param.name for param in solved]
         self._ctx = None
+        self._data_ctx = None
+
+    def set_data_batch(self, data):
+        """Give the Fisher context the data vectors ``data`` (array ``[M, n_data]`` in ``flatdata`` order, or a list of per-observable arrays: ``likelihood.data_batch``)
+        for :meth:`evaluate` with ``data_index``; ``None`` drops them.  The context that holds them is a private one: the likelihood's own is shared with its samplers.
+        Returns the number of data vectors."""
+        if data is None:
+            if self._data_ctx is not None: self._data_ctx.close()
+            self._data_ctx = None
+            return 0
+        from ._lib import Context, check_data_batch
+        from .likelihoods.base import flatten_data_batch
+        like = getattr(self.likelihood, '_fused', self.likelihood)
+        sizes = [obs.wmatrix.size for obs in like.observables]
+        flatdata = check_data_batch(flatten_data_batch(data, sizes), sum(sizes))      # (before any device call)
+        if self._data_ctx is None:
+            # every solved and '.prec' parameter is varied here: the configuration holds the likelihood's data vector as it is, nothing to add to the batch
+            self._data_ctx = Context(like._spec({}, like._flatdata_list(), like._precision_input, vary_solved=bool(self._solved_names)), device=like.device)
+        return self._data_ctx.set_data_batch(flatdata)
 
     def _get_context(self):
         if self._ctx is None:
@@ -126,10 +145,22 @@ class Fisher(object):
             raise ValueError('zero finite-difference interval: a centre sits on both prior bounds of a parameter')
         return np.clip(steps, 0., None)
 
-    def evaluate(self, centers):
-        """``centers [B, P]`` (columns ordered as :attr:`varied_params`) -> (offset [B], gradient [B, P], hessian [B, P, P]) of the likelihood term, one GPU batch."""
+    def evaluate(self, centers, data_index=None):
+        """``centers [B, P]`` (columns ordered as :attr:`varied_params`) -> (offset [B], gradient [B, P], hessian [B, P, P]) of the likelihood term, one GPU batch.
+        ``data_index [B]``: centre b against data vector ``data_index[b]`` of :meth:`set_data_batch` (``dl_eval_fisher_data``: the finite-difference route only)."""
         import torch
         centers = np.ascontiguousarray(np.atleast_2d(centers), dtype='f8')
+        if data_index is not None:
+            if self.method == 'analytic': raise NotImplementedError('the analytic Fisher does not take a data batch: use method="finite"')
+            if self._data_ctx is None: raise ValueError('no data batch: call set_data_batch first')
+            data_index = np.asarray(data_index)
+            if data_index.shape != (centers.shape[0],) or not np.issubdtype(data_index.dtype, np.integer):
+                raise ValueError('data_index must be {:d} integers'.format(centers.shape[0]))
+            ctx = self._data_ctx
+            device = torch.device('cuda', ctx.device)
+            hessian, gradient, offset = ctx.eval_fisher_data(torch.as_tensor(centers, device=device), torch.as_tensor(self.steps(centers), device=device).contiguous(),
+                                                             torch.as_tensor(np.ascontiguousarray(data_index, dtype='i4'), device=device))
+            return offset.cpu().numpy(), gradient.cpu().numpy(), hessian.cpu().numpy()
         ctx = self._get_context()
         device = torch.device('cuda', ctx.device)
         if self.method == 'analytic' or (self.method == 'auto' and (self.AUTO_EMULATED or not getattr(ctx, 'emulated', False))):

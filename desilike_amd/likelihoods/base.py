@@ -139,6 +139,77 @@ def _collect_varied(observables):
     return all_params
 
 
+def flatten_data_batch(data, sizes):
+    """Data vectors of a batch as one array ``[M, sum(sizes)]`` in ``flatdata`` order (observable after observable).  ``data``: that array itself (or one vector), or a
+    list with one entry per observable, in the order the likelihood's constructor takes them, entry i holding the ``M`` vectors ``[M, sizes[i]]`` of observable i.
+    Raises :class:`ValueError` for anything else; no device call."""
+    sizes = [int(size) for size in sizes]
+    total = sum(sizes)
+    try:
+        array = np.asarray(data, dtype='f8')
+    except (ValueError, TypeError):
+        array = None            # ragged: observables of different sizes
+    if array is not None and array.ndim == 1 and array.size == total: return array[None, :]
+    if array is not None and array.ndim == 2 and array.shape[1] == total: return array
+    if isinstance(data, (list, tuple)) and len(data) == len(sizes):
+        blocks = [np.atleast_2d(np.asarray(block, dtype='f8')) for block in data]
+        if all(block.ndim == 2 and block.shape[1] == size for block, size in zip(blocks, sizes)) and len({block.shape[0] for block in blocks}) == 1:
+            return np.concatenate(blocks, axis=1)
+        raise ValueError('a data batch given observable by observable needs one array (M, size) per observable with sizes {}, found shapes {}'.format(sizes, [block.shape for block in blocks]))
+    raise ValueError('a data batch is an array (M, {:d}) or a list of {:d} per-observable arrays (M, size) with sizes {}, found shape {}'.format(
+        total, len(sizes), sizes, getattr(array, 'shape', None)))
+
+
+class DataBatch(object):
+    """``likelihood.data_batch(data)``: the log-posterior of one likelihood against MANY data vectors ("fit every mock") -- one theory evaluation and one window product
+    per point whatever the number of data vectors (``dl_data_set`` / ``dl_eval_logposterior_data``; csrc/dl_data_batch.h).
+
+    The context behind it is a private one (the likelihood's own contexts are shared with its samplers), compiled from the configuration samplers consume
+    (:meth:`ObservablesGaussianLikelihood._get_posterior_context`): the plain context without analytically solved parameters; the marginalised-precision context when
+    every solved parameter has a constant derivative row -- the data shift ``(x0 - loc) T`` of that construction is added to every data vector and its offset to every
+    value.  Point-dependent solved rows (velocileptors counter terms) are out of scope: ``NotImplementedError``."""
+
+    def __init__(self, likelihood, data):
+        from .._lib import Context, check_data_batch
+        likelihood.initialize()
+        self.likelihood = likelihood
+        sizes = [obs.wmatrix.size for obs in likelihood.observables]
+        flatdata = check_data_batch(flatten_data_batch(data, sizes), sum(sizes))     # (shape and finiteness: before any device call)
+        solved = likelihood.solved_params
+        if len(solved) and not likelihood._solved_are_constant():
+            raise NotImplementedError('data batch with analytically solved parameters whose derivative rows depend on the point ({}): use GaussNewtonProfiler.maximize_batch, '
+                                      'which varies them with the other parameters'.format(solved.names()))
+        likelihood._get_posterior_context()
+        key = ('posterior',) if len(solved) else ()
+        spec = likelihood._context_specs[key]
+        # what the configuration did to the likelihood's own data vector ('.prec' shift, Gaussian priors of the solved parameters) is done to every vector of the batch
+        self.shift = np.concatenate([np.ravel(ospec['flatdata']) for ospec in spec['observables']]) - np.concatenate(likelihood._flatdata_list())
+        self.offset = float(getattr(likelihood, '_posterior_offsets', {}).get(key, 0.))
+        self.flatdata = flatdata
+        self.context = Context(spec, device=likelihood.device)
+        self.context.set_data_batch(flatdata + self.shift)
+
+    @property
+    def size(self):
+        return self.flatdata.shape[0]
+
+    def logposterior(self, values, index=None):
+        """``values [B, n_varied]`` (columns ordered as ``likelihood.varied_params``) -> log-posterior ``[B, M]`` of every point given every data vector; with
+        ``index [B]`` (integers in ``[0, M)``) -> ``[B]``, point b given data vector ``index[b]``.  Samplers' conventions: -inf outside the prior."""
+        values = np.ascontiguousarray(np.atleast_2d(values), dtype='f8')
+        nvaried = len(self.likelihood.varied_params)
+        if values.shape[1] != nvaried:
+            raise ValueError('values must have shape (B, {:d}), found {}'.format(nvaried, values.shape))
+        if index is not None:
+            index = np.asarray(index)
+            if index.shape != (values.shape[0],) or not np.issubdtype(index.dtype, np.integer):
+                raise ValueError('index must be {:d} integers, found shape {} and type {}'.format(values.shape[0], index.shape, index.dtype))
+            if index.size and (index.min() < 0 or index.max() >= self.size):
+                raise ValueError('index must lie in [0, {:d})'.format(self.size))
+        out, _ = self.context.eval_logposterior_data_host(values, index=index)
+        return out + self.offset
+
+
 class ObservablesGaussianLikelihood(BaseGaussianLikelihood):
     """
     Gaussian likelihood of observables (likelihoods/base.py:504-712).
@@ -715,6 +786,10 @@ class ObservablesGaussianLikelihood(BaseGaussianLikelihood):
                     logposterior += offset
         return logposterior
 
+    def data_batch(self, data):
+        """This likelihood against many data vectors: :class:`DataBatch` (``data``: array ``[M, n_data]`` in ``flatdata`` order, or a list of per-observable arrays)."""
+        return DataBatch(self, data)
+
     @property
     def size(self):
         return len(self.flatdata)
@@ -779,6 +854,11 @@ class SumLikelihood(BaseLikelihood):
     def evaluate_logposterior(self, *args, **kwargs):
         self.initialize()
         return self._fused.evaluate_logposterior(*args, **kwargs)
+
+    def data_batch(self, data):
+        """:meth:`ObservablesGaussianLikelihood.data_batch` of the fused likelihood: the observables of the members one after the other."""
+        self.initialize()
+        return self._fused.data_batch(data)
 
     @property
     def size(self):

@@ -42,15 +42,21 @@ class Profiles(object):
         return cls(state['start'], state['bestfit'], state['error'], tuple(state['covariance']), attrs=state.get('attrs', None))
 
 
-def levenberg_marquardt(evaluate, start, lower, upper, max_iterations=100, xtol=1e-7, ftol=1e-9, damping=1e-3, free=None):
+def levenberg_marquardt(evaluate, start, lower, upper, max_iterations=100, xtol=1e-7, ftol=1e-9, damping=1e-3, free=None, with_rows=False):
     """Maximise f over a batch of starts.  ``evaluate(points [S, P]) -> (f [S], gradient [S, P], curvature [S, P, P])`` with ``curvature`` positive semi-definite
     (minus the Gauss-Newton Hessian); ``lower`` / ``upper``: bounds [P].  Per iteration ONE call of ``evaluate`` on the candidates of the starts still running: a
     candidate that improves f is taken (its derivatives are already there) and the damping relaxed, otherwise the damping grows and the step is redone from the kept
     derivatives.  Stops a start when an accepted step is below ``xtol`` in units of the curvature's standard deviations or improves f by less than ``ftol``.
     ``free``: boolean mask [P] (or [S, P]) of the coordinates that move; the others keep their starting values (profiles along a parameter).
+    ``with_rows``: ``evaluate(points, rows)`` also receives the rows of ``start`` the points belong to (objectives that differ from start to start: one data vector
+    per row, :meth:`GaussNewtonProfiler.maximize_batch`).
     Returns (points, f, gradient, curvature, iterations [S], converged [S])."""
     x = np.array(start, dtype='f8')
     S, P = x.shape
+    if with_rows:
+        evaluate_rows = evaluate
+        rows = [np.arange(S)]
+        evaluate = lambda points: evaluate_rows(points, rows[0])
     free = np.ones((S, P), dtype='?') if free is None else np.broadcast_to(np.asarray(free, dtype='?'), (S, P))
     f, g, H = evaluate(x)
     f, g, H = np.array(f, dtype='f8'), np.array(g, dtype='f8'), np.array(H, dtype='f8')
@@ -77,6 +83,7 @@ def levenberg_marquardt(evaluate, start, lower, upper, max_iterations=100, xtol=
             step[m] = np.linalg.solve((H[s] + lam[s] * np.diag(diag))[np.ix_(m, m)], g[s][m])      # (H + lam diag H) step = gradient, in the moving coordinates
             candidates[slot] = np.where(m, np.clip(x[s] + step, lo, hi), x[s])
             scaled[slot] = np.max(np.abs(candidates[slot] - x[s]) * np.sqrt(diag))   # step in units of the (conditional) standard deviations
+        if with_rows: rows[0] = index
         fc, gc, Hc = evaluate(candidates)
         iterations[index] += 1
         for slot, s in enumerate(index):
@@ -124,9 +131,9 @@ class GaussNewtonProfiler(BasePosteriorSampler):
                 curvature[ok, ip] = np.maximum(-(up[ok] - 2. * mid[ok] + dn[ok]) / h**2, 0.)
         return value, gradient, curvature
 
-    def _evaluate(self, points):
+    def _evaluate(self, points, data_index=None):
         points = np.ascontiguousarray(points, dtype='f8')
-        offset, gradient, hessian = self.fisher.evaluate(points)
+        offset, gradient, hessian = self.fisher.evaluate(points) if data_index is None else self.fisher.evaluate(points, data_index=data_index)
         value, pgradient, pcurvature = self._prior_terms(points)
         curvature = -hessian
         index = np.arange(points.shape[1])
@@ -153,6 +160,13 @@ class GaussNewtonProfiler(BasePosteriorSampler):
         lower = np.array([param.prior.limits[0] for param in self.params], dtype='f8')
         upper = np.array([param.prior.limits[1] for param in self.params], dtype='f8')
         x, f, g, H, iterations, converged = levenberg_marquardt(self._evaluate, start, lower, upper, max_iterations=max_iterations, xtol=xtol, ftol=ftol)
+        self.profiles = self._profiles(names, start, x, f, g, H, iterations, converged)
+        if self.save_fn is not None: self.profiles.save(self.save_fn)
+        return self.profiles
+
+    @staticmethod
+    def _profiles(names, start, x, f, g, H, iterations, converged):
+        """:class:`Profiles` of the starts of one maximisation."""
         covariances = []
         for s in range(x.shape[0]):
             try: covariances.append(np.linalg.inv(H[s]))
@@ -162,10 +176,40 @@ class GaussNewtonProfiler(BasePosteriorSampler):
         bestfit = {name: x[:, ip].copy() for ip, name in enumerate(names)}
         bestfit['logposterior'] = f.copy()
         error = {name: np.sqrt(np.abs(covariances[:, ip, ip])) for ip, name in enumerate(names)}
-        self.profiles = Profiles({name: start[:, ip].copy() for ip, name in enumerate(names)}, bestfit, error, (names, covariances[best]),
-                                 attrs={'iterations': iterations.tolist(), 'converged': converged.tolist(), 'gradient_norm': np.abs(g / np.sqrt(np.maximum(H[:, np.arange(len(names)), np.arange(len(names))], 1e-300))).max(axis=1).tolist()})
-        if self.save_fn is not None: self.profiles.save(self.save_fn)
-        return self.profiles
+        return Profiles({name: start[:, ip].copy() for ip, name in enumerate(names)}, bestfit, error, (names, covariances[best]),
+                        attrs={'iterations': iterations.tolist(), 'converged': converged.tolist(), 'gradient_norm': np.abs(g / np.sqrt(np.maximum(H[:, np.arange(len(names)), np.arange(len(names))], 1e-300))).max(axis=1).tolist()})
+
+    def maximize_batch(self, data, nstarts=1, start=None, max_iterations=100, xtol=1e-7, ftol=1e-9):
+        """Maximise the log-posterior given each of the ``M`` data vectors of ``data`` (array ``[M, n_data]`` in ``flatdata`` order, or a list of per-observable arrays:
+        ``likelihood.data_batch``) -- "fit every mock" -- from ``nstarts`` starts each: all ``M x nstarts`` starts are rows of ONE Levenberg-Marquardt batch, the data
+        vector of a row is its mock (``dl_eval_fisher_data``: the Gauss-Newton curvature does not depend on the data, only the residual does).  ``start``: ``[nstarts, P]``
+        (the same starts for every mock) or ``[M, nstarts, P]``, columns ordered as ``self.params``; default: ``nstarts`` draws from the ``ref`` distributions, shared by
+        the mocks.  Solved parameters are varied, as in :meth:`maximize`.  Returns a list of ``M`` :class:`Profiles`."""
+        if self.fisher.method == 'analytic':
+            raise NotImplementedError('maximize_batch differentiates by finite differences (the analytic Jacobian route does not take a data batch): use derivatives="finite"')
+        M = self.fisher.set_data_batch(data)
+        names = [param.name for param in self.params]
+        if start is None: start = self._get_start_points(int(nstarts))
+        start = np.asarray(start, dtype='f8')
+        if start.ndim < 3: start = np.broadcast_to(np.atleast_2d(start), (M,) + np.atleast_2d(start).shape)
+        if start.ndim != 3 or start.shape[0] != M or start.shape[2] != len(names):
+            raise ValueError('start must have shape (nstarts, {0:d}) or ({1:d}, nstarts, {0:d}), columns {2}'.format(len(names), M, names))
+        nstarts = start.shape[1]
+        start = np.ascontiguousarray(start.reshape(M * nstarts, len(names)))
+        mock = np.repeat(np.arange(M, dtype='i4'), nstarts)
+        lower = np.array([param.prior.limits[0] for param in self.params], dtype='f8')
+        upper = np.array([param.prior.limits[1] for param in self.params], dtype='f8')
+        method, self.fisher.method = self.fisher.method, 'finite'
+        try:
+            x, f, g, H, iterations, converged = levenberg_marquardt(lambda points, rows: self._evaluate(points, data_index=mock[rows]), start, lower, upper,
+                                                                    max_iterations=max_iterations, xtol=xtol, ftol=ftol, with_rows=True)
+        finally:
+            self.fisher.method = method
+        toret = []
+        for m in range(M):
+            sl = slice(m * nstarts, (m + 1) * nstarts)
+            toret.append(self._profiles(names, start[sl], x[sl], f[sl], g[sl], H[sl], iterations[sl], converged[sl]))
+        return toret
 
     def profile(self, params=None, size=30, cl=2., max_iterations=100, xtol=1e-7, ftol=1e-9):
         """1D profiles (profilers/base.py ``profile``): for ``size`` values of each parameter within ``cl`` errors of the best fit, the posterior maximised over all the

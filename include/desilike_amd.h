@@ -207,6 +207,26 @@ int  dl_eval_logposterior(dl_ctx* ctx, const double* theta_dev, int64_t B, doubl
  * D = flattheory - flatdata.  Outputs (any may be NULL): hessian_dev [B, P, P], gradient_dev [B, P], offset_dev [B].  The context must have no analytically
  * solved parameter (vary them: the reference's Fisher does the same, fisher.py:688-695); P <= 31.  Asynchronous on ``hip_stream``. */
 int  dl_eval_fisher(dl_ctx* ctx, const double* centers_dev, const double* steps_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, void* hip_stream);
+
+/* Data batch: M data vectors held by the context NEXT TO its own ("fit the same likelihood to each of M mocks": one theory evaluation and one GEMM per point,
+ * whatever M -- the data enter the whitened residual through its additive term L^T (bias - flatdata) only; csrc/dl_data_batch.h).
+ * dl_data_set: ``flatdata`` (host) [M, n_data], rows in the order of the context's own data vector (observable after observable).  Each row is whitened by the host
+ * arithmetic dl_create applies to the context's own vector (block structure of the factor, "precision_factor" contexts and aligned row ranges included) and
+ * [M, N_pad] doubles are uploaded into storage of the context.  A second call replaces the batch, M = 0 frees it; dl_info "n_data_batch" returns M.  Synchronises
+ * the device.  Returns 1 (message in dl_last_error; the batch held before is kept when the arguments are refused) for a context with an observable transform or
+ * with analytically solved parameters, a NaN or infinite data value, M < 0 or M > 65536.  No other entry point reads the batch: their results do not change. */
+int  dl_data_set(dl_ctx* ctx, const double* flatdata, int32_t M);
+/* Log-posteriors against the data batch, conventions of dl_eval_logposterior (loglike + logprior; -inf for NaN inputs, points outside the prior or a non-finite
+ * likelihood).  data_index_dev == NULL ("cross"): out_dev [B, M] row-major, point b given data vector m.  Otherwise ("paired"): out_dev [B], point b given data
+ * vector data_index_dev[b]; an index outside [0, M) gives that row NaN and DL_STATUS_NAN_INPUT (the table is not read).  cross[b, m] and paired[b] with index m are
+ * the same bits.  status_dev [B] optional; in cross mode it describes the point (NaN input, out of prior, non-finite theory).  Always the residual route (theory
+ * kernels or the emulated feature path, split-K window GEMM or feature GEMM, then the finalize of csrc/dl_data_batch.h: direct differences, a fixed accumulation
+ * order).  Works in passes over B like dl_eval_batch.  Returns 1 without a data batch.  Asynchronous on ``hip_stream``. */
+int  dl_eval_logposterior_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, double* out_dev, int32_t* status_dev, void* hip_stream);
+/* dl_eval_fisher with the residual of centre b taken against data vector data_index_dev[b] of the data batch: same stencil, outputs, conventions (no 1/2) and limits
+ * (P <= 31, no solved parameter).  The Hessian does not depend on the data.  An index outside [0, M): NaN offset and gradient for that centre. */
+int  dl_eval_fisher_data(dl_ctx* ctx, const double* centers_dev, const double* steps_dev, int64_t B, const int32_t* data_index_dev, double* hessian_dev, double* gradient_dev,
+                         double* offset_dev, void* hip_stream);
 /* The same Fisher algebra from EXACT derivatives (what the reference's Differentiation takes from jax when it is present, desilike/differentiation.py; the
  * finalisation of fisher.py:731-750 then works on an exact dD): dD = W~ . d(theory vector) / d theta, the rows d(theory vector) / d theta_p written by the
  * forward-mode twin of the gradient kernel (csrc/dl_fullshape_jac.h: qpar / qper through every AP mode, df, dm, dn, b1 of either tracer, sn0) -- no steps, one theory

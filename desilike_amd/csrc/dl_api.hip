@@ -65,6 +65,7 @@ struct dl_ctx {
     std::vector<DlObsDev> obs_kernarg; // observables with device pointers, passed by value to the theory kernel
     DlObsDev* obs_array_dev = nullptr; // the same structs in device memory (one theory launch for several observables)
     double* priors_dev = nullptr;    // [P, 5]
+    double* prior_rec_ws = nullptr;  // [cap] summed log-priors | [cap] int32 flags: the prior record of the step's theory launch (dl_prior.h), with the workspaces of dl_reserve
     int32_t* gemm_counters = nullptr;// [<= 2048 / 32 + 8] arrival counters of the fused chi2 GEMM finalize (zero between launches)
     int32_t* step_ready = nullptr;   // [32 + 8] arrival counters of the row blocks' producers in dl_step_kernel (zero between launches); behind gemm_counters in one allocation
     double* wt_white_dev = nullptr;  // [N_pad, K_pad]  L^T . blockdiag(W_obs)          (chi2 path)
@@ -560,7 +561,7 @@ void dl_destroy(dl_ctx* ctx) {
     if (ctx->data_index_ws) (void)hipFree(ctx->data_index_ws);
     void* ptrs[] = {ctx->arena_dev, ctx->priors_dev, ctx->wt_white_dev, ctx->wt_frag_dev, ctx->bias_white_dev, ctx->wt_full_dev, ctx->bias_full_dev, ctx->wh_dev,
                     ctx->bias_wh_dev, ctx->flatdata_dev, ctx->transform_dev, ctx->tconst_dev, ctx->power_ws, ctx->delta_ws, ctx->flat_ws, ctx->stencil_ws, ctx->theta_stage, ctx->out_stage,
-                    ctx->status_stage, ctx->gemm_counters, ctx->obs_array_dev, ctx->ws_scratch};
+                    ctx->status_stage, ctx->gemm_counters, ctx->obs_array_dev, ctx->ws_scratch, ctx->prior_rec_ws};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (double* p : ctx->gfrag_dev) if (p) (void)hipFree(p);
     for (auto& ob : ctx->obs) if (ob.tns) { dl_tns_destroy(ob.tns); ob.tns = nullptr; }
@@ -608,7 +609,7 @@ static int dl_reserve(dl_ctx* ctx, int64_t B) {
     if (need <= ctx->cap) return 0;
     need = std::min<int64_t>(std::max<int64_t>(need, 1024), DL_CHUNK);
     if (ctx->cap > 0) DL_HIP_CHECK(ctx, hipDeviceSynchronize());   // kernels of earlier calls (any stream) may still read the workspaces about to be freed
-    for (double** p : {&ctx->power_ws, &ctx->delta_ws, &ctx->flat_ws, &ctx->feat_ws, &ctx->stencil_ws, &ctx->ws_scratch}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    for (double** p : {&ctx->power_ws, &ctx->delta_ws, &ctx->flat_ws, &ctx->feat_ws, &ctx->stencil_ws, &ctx->ws_scratch, &ctx->prior_rec_ws}) if (*p) { (void)hipFree(*p); *p = nullptr; }
     ctx->cap = 0;
     const size_t R = 1 + ctx->n_var;   // rows per point: power + point-dependent derivative rows (analytic marginalisation)
     DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->power_ws, (size_t)need * R * ctx->K_pad * sizeof(double)));
@@ -617,6 +618,7 @@ static int dl_reserve(dl_ctx* ctx, int64_t B) {
     DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->flat_ws, (size_t)need * ctx->N_pad * sizeof(double)));
     if (ctx->feat_ok) DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->feat_ws, (size_t)need * ctx->feat_ld * sizeof(double)));
     DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->stencil_ws, (size_t)need * ctx->n_params * sizeof(double)));
+    DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->prior_rec_ws, (size_t)need * 2 * sizeof(double)));
     if (ctx->ws_ld > 0) {
         // the template scratch moved: the observables' descriptions (host copies and the device array of the merged launches) point at their blocks of it
         DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->ws_scratch, (size_t)need * ctx->ws_ld * sizeof(double)));
@@ -635,6 +637,7 @@ static int dl_reserve(dl_ctx* ctx, int64_t B) {
     DL_HIP_CHECK(ctx, hipMemset(ctx->flat_ws, 0, (size_t)need * ctx->N_pad * sizeof(double)));
     if (ctx->feat_ok) DL_HIP_CHECK(ctx, hipMemset(ctx->feat_ws, 0, (size_t)need * ctx->feat_ld * sizeof(double)));
     DL_HIP_CHECK(ctx, hipMemset(ctx->stencil_ws, 0, (size_t)need * ctx->n_params * sizeof(double)));
+    DL_HIP_CHECK(ctx, hipMemset(ctx->prior_rec_ws, 0, (size_t)need * 2 * sizeof(double)));
     // the memsets run on the null stream and may still be in flight when this returns; the caller's stream (the private host stream, torch's side streams) is a
     // non-blocking one that does not wait for the null stream: without this synchronisation its kernels could be overtaken by the zeroing of the buffer they write
     // (seen once as a 2.6e-6 error on one row of the first large batch of a context, in a child of tests/test_gpu_switches.py running beside three others)
@@ -688,27 +691,31 @@ static int dl_eval_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, double*
         // -0.5 us per 1024 points)
         const int xcd_local = dl_options().xcd_local;   // 0: off, 1: chi2 GEMM path, 2: also the large-batch GEMM
         const bool chi2_fused_env_early = dl_options().chi2_fused;
-        const bool chi2_fused_early = chi2_fused_env_early && !ctx->priors_general;
+        const bool chi2_fused_early = chi2_fused_env_early && chi2_path && !dl_options().fs_no_prior;   // (the fused finalize reads the prior record)
         const int xcd_block = !xcd_local ? 0 : chi2_path ? (chi2_fused_early ? 32 : dl_chi2_gemm_row_tile(nb, ctx->N_pad)) : (xcd_local > 1 && !feat_path && !ctx->any_transform && ctx->n_solved == 0 && ctx->N_pad == 128) ? 64 : 0;
         // the whole step in one launch (dl_step_kernel): plain likelihood of one Kaiser-type observable in its fast instantiation, <= 1024 points in whole groups of 256
         // OFF by default (DL_STEP_KERNEL=1 selects it): measured 31.1 us per 1024-point step against 24.4 us for the three launches -- in-kernel stamps (profiles/r05c_step_stamps.txt):
         // theory of four points under ONE workgroup barrier 14.4 us (four independent workgroups per CU: ~8.5), publish 1.1, wait for the row block 2.0 - 2.5, GEMM + finalize 11.1;
         // even with the theory phase at its stand-alone time the sum is what the three launches take: the step is bound by the lives of its workgroups, not by its launch boundaries
         const bool step_kernel_allowed = dl_options().step_kernel;
-        if (step_kernel_allowed && chi2_path && !need_flat && ctx->n_obs == 1 && !ctx->priors_general && ctx->K_pad % 128 == 0 &&
+        // plain-likelihood chi2-GEMM step: the theory launch also writes the theta-only part of the result, the prior record (DL_FS_NO_PRIOR=1: the finalize evaluates the priors)
+        DlPriorRec prior_rec;
+        if (chi2_path && !dl_options().fs_no_prior) { prior_rec.priors = ctx->priors_dev; prior_rec.lp = ctx->prior_rec_ws; prior_rec.flag = reinterpret_cast<int32_t*>(ctx->prior_rec_ws + ctx->cap); }
+        if (step_kernel_allowed && chi2_path && prior_rec.lp != nullptr && !need_flat && ctx->n_obs == 1 && ctx->K_pad % 128 == 0 &&
             dl_step_lds_bytes(ctx->obs_kernarg[0], nb, ctx->N_pad) != 0) {
             prof_phase(0);
             dl_launch_step(ctx->obs_kernarg[0], th, P, nb, ctx->power_ws, ctx->K_pad, ctx->wt_white_dev, ctx->K_pad, ctx->bias_white_dev, ctx->delta_ws, ctx->K_pad, ctx->K_live,
-                           ctx->gemm_counters, ctx->step_ready, 8, ctx->priors_dev, loglike_dev ? loglike_dev + b0 : nullptr, logprior_dev ? logprior_dev + b0 : nullptr,
+                           ctx->gemm_counters, ctx->step_ready, 8, prior_rec, loglike_dev ? loglike_dev + b0 : nullptr, logprior_dev ? logprior_dev + b0 : nullptr,
                            status_dev ? status_dev + b0 : nullptr, post_mode, stream, ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data());
             prof_phase(-1);
             if (prof) ctx->prof_calls++;
             continue;
         }
         prof_phase(0);
+        bool have_rec = false;
         if (!(feat_path && emu_fused))
-            dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, th, P, nb, ctx->power_ws, ctx->K_pad, nullptr, 0, stream, feat_path ? ctx->feat_ws : nullptr, ctx->feat_ld,
-                                xcd_block, ctx->obs_array_dev);
+            have_rec = dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, th, P, nb, ctx->power_ws, ctx->K_pad, nullptr, 0, stream, feat_path ? ctx->feat_ws : nullptr, ctx->feat_ld,
+                                           xcd_block, ctx->obs_array_dev, true, &prior_rec);
         prof_phase(1);
         int n_slabs = 1, cps = 0;
         int64_t slab_stride = 0;
@@ -762,11 +769,11 @@ static int dl_eval_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, double*
         // DL_CHI2_FUSED=1: finalize inside the GEMM's last-arriving workgroups.  Off by default: measured 19.1 us (GEMM 17.1) against 17.5 us for GEMM + the
         // separate 1024-thread finalize launch -- the device-scope counter round trip and the dependent tail cost more than the launch they save.
         const bool chi2_fused_env = dl_options().chi2_fused;
-        const bool chi2_fused = chi2_fused_env && !ctx->priors_general;   // (the experimental fused finalize of the GEMM knows uniform / norm priors only)
+        const bool chi2_fused = chi2_fused_env && have_rec;   // (the fused finalize adds the log-priors of the record: without one, the separate launches)
         if (chi2_path) {
             if (nb > 16384) { prof_phase(-1); return dl_fail(ctx, "dl_eval_batch: DL_CHI2_GEMM_MAX above 16384 rows"); }
             dl_launch_chi2_gemm(ctx->power_ws, ctx->K_pad, ctx->wt_white_dev, ctx->K_pad, ctx->bias_white_dev, ctx->delta_ws, nb, ctx->N_pad, ctx->K_pad,
-                                chi2_fused ? ctx->gemm_counters : nullptr, th, P, ctx->priors_dev, loglike_dev ? loglike_dev + b0 : nullptr,
+                                chi2_fused ? ctx->gemm_counters : nullptr, chi2_fused ? &prior_rec : nullptr, loglike_dev ? loglike_dev + b0 : nullptr,
                                 logprior_dev ? logprior_dev + b0 : nullptr, status_dev ? status_dev + b0 : nullptr, post_mode, stream,
                                 ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data(), ctx->K_live, nullptr, 0, ctx->wt_frag_dev);
         } else if (chi2_big) {
@@ -795,7 +802,10 @@ static int dl_eval_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, double*
             // finalize fused into the GEMM
         } else if (finalized_in_kernel) {
             // marginalised finalize in the tail of the fused emulator / feature-GEMM kernel
-        } else if (chi2_path || chi2_big)
+        } else if (chi2_path && have_rec)
+            dl_launch_finalize_rec(ctx->delta_ws, part_tiles, prior_rec, nb, loglike_dev ? loglike_dev + b0 : nullptr, logprior_dev ? logprior_dev + b0 : nullptr,
+                                   status_dev ? status_dev + b0 : nullptr, post_mode, stream);
+        else if (chi2_path || chi2_big)
             dl_launch_finalize_part(ctx->delta_ws, part_tiles, th, P, ctx->priors_dev, nb, loglike_dev ? loglike_dev + b0 : nullptr, logprior_dev ? logprior_dev + b0 : nullptr,
                                     status_dev ? status_dev + b0 : nullptr, post_mode, stream);
         else if (ctx->n_solved > 0)
@@ -1078,7 +1088,7 @@ int dl_eval_fisher_analytic(dl_ctx* ctx, const double* centers_dev, int64_t B, d
         const int64_t nc = std::min<int64_t>(per_pass, B - b0), nr = nc * P;
         const double* th = centers_dev + (size_t)b0 * P;
         dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, th, P, nc, ctx->power_ws, Kp, nullptr, 0, stream, nullptr, 0, xcd_local ? dl_chi2_gemm_row_tile(nc, Np) : 0, ctx->obs_array_dev);
-        dl_launch_chi2_gemm(ctx->power_ws, Kp, ctx->wt_white_dev, Kp, ctx->bias_white_dev, ctx->delta_ws, nc, Np, Kp, nullptr, th, P, ctx->priors_dev, nullptr, nullptr, nullptr, 1, stream,
+        dl_launch_chi2_gemm(ctx->power_ws, Kp, ctx->wt_white_dev, Kp, ctx->bias_white_dev, ctx->delta_ws, nc, Np, Kp, nullptr, nullptr, nullptr, nullptr, nullptr, 1, stream,
                             ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data(), ctx->K_live, ctx->fa_resid, Np, ctx->wt_frag_dev);
         dl_launch_fullshape_jac(ctx->obs_kernarg.data(), ctx->n_obs, ctx->obs_array_dev, th, P, nc, ctx->K_live, Kp, ctx->fa_jac, Kp, stream);
         int cps = 0;
@@ -1223,7 +1233,7 @@ int dl_eval_logposterior_grad(dl_ctx* ctx, const double* theta_dev, int64_t B, d
         int32_t* st = status_dev ? status_dev + b0 : ctx->grad_status;      // (the gradient's finalize needs the status whether the caller wants it or not)
         dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, th, P, nb, ctx->power_ws, ctx->K_pad, nullptr, 0, stream, nullptr, 0, xcd_local ? dl_chi2_gemm_row_tile(nb, Np) : 0, ctx->obs_array_dev,
                             false);   // (the value from the interval polynomials the gradient kernel differentiates)
-        dl_launch_chi2_gemm(ctx->power_ws, Kp, ctx->wt_white_dev, Kp, ctx->bias_white_dev, ctx->delta_ws, nb, Np, Kp, nullptr, th, P, ctx->priors_dev, nullptr, nullptr, nullptr, 1, stream,
+        dl_launch_chi2_gemm(ctx->power_ws, Kp, ctx->wt_white_dev, Kp, ctx->bias_white_dev, ctx->delta_ws, nb, Np, Kp, nullptr, nullptr, nullptr, nullptr, nullptr, 1, stream,
                             ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data(), ctx->K_live, ctx->grad_delta, Np, ctx->wt_frag_dev);
         dl_launch_finalize_part(ctx->delta_ws, Np / 16, th, P, ctx->priors_dev, nb, logposterior_dev + b0, nullptr, st, 1, stream);
         // Y = -d~ W~: [nb, N_pad] x [N_pad, K_pad] through the LDS-DMA tiled GEMM, one split (K = N_pad: 4 panels), no bias
@@ -1525,8 +1535,8 @@ int dl_internal_eval_fold(dl_ctx* ctx, const DlEnsFold& fold, int64_t B, double*
     if (dl_reserve(ctx, B)) return 1;
     const int xcd_local = dl_options().xcd_local;
     if (!dl_launch_fullshape_ens(ctx->obs_kernarg.data(), ctx->n_obs, ctx->obs_array_dev, fold, B, ctx->power_ws, ctx->K_pad, xcd_local ? dl_chi2_gemm_row_tile(B, ctx->N_pad) : 0, stream)) return 2;
-    dl_launch_chi2_gemm(ctx->power_ws, ctx->K_pad, ctx->wt_white_dev, ctx->K_pad, ctx->bias_white_dev, part_out, B, ctx->N_pad, ctx->K_pad, nullptr, nullptr, ctx->n_params,
-                        ctx->priors_dev, nullptr, nullptr, nullptr, 1, stream, ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data(), ctx->K_live, nullptr, 0, ctx->wt_frag_dev);
+    dl_launch_chi2_gemm(ctx->power_ws, ctx->K_pad, ctx->wt_white_dev, ctx->K_pad, ctx->bias_white_dev, part_out, B, ctx->N_pad, ctx->K_pad, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, 1, stream, ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data(), ctx->K_live, nullptr, 0, ctx->wt_frag_dev);
     DL_HIP_CHECK(ctx, hipGetLastError());
     return 0;
 }
@@ -1542,8 +1552,8 @@ int dl_internal_eval_partials(dl_ctx* ctx, const double* theta_dev, int64_t B, c
     if (dl_reserve(ctx, B)) return 1;
     const int xcd_local = dl_options().xcd_local;
     dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, theta_dev, ctx->n_params, B, ctx->power_ws, ctx->K_pad, nullptr, 0, stream, nullptr, 0, xcd_local ? dl_chi2_gemm_row_tile(B, ctx->N_pad) : 0, ctx->obs_array_dev);
-    dl_launch_chi2_gemm(ctx->power_ws, ctx->K_pad, ctx->wt_white_dev, ctx->K_pad, ctx->bias_white_dev, ctx->delta_ws, B, ctx->N_pad, ctx->K_pad, nullptr, theta_dev, ctx->n_params,
-                        ctx->priors_dev, nullptr, nullptr, nullptr, 1, stream, ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data(), ctx->K_live, nullptr, 0, ctx->wt_frag_dev);
+    dl_launch_chi2_gemm(ctx->power_ws, ctx->K_pad, ctx->wt_white_dev, ctx->K_pad, ctx->bias_white_dev, ctx->delta_ws, B, ctx->N_pad, ctx->K_pad, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, 1, stream, ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data(), ctx->K_live, nullptr, 0, ctx->wt_frag_dev);
     *part = ctx->delta_ws;
     *n_tiles = ctx->N_pad / 16;
     *priors = ctx->priors_dev;

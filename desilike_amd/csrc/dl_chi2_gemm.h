@@ -34,16 +34,16 @@ typedef double dl_cg_double4 __attribute__((ext_vector_type(4)));
 #define DL_CG_LDS_BYTES (DL_CG_NBUF * DL_CG_ROWS * DL_CG_LD * 8)   // (32-row tile; the 16-row tile uses the same allocation)
 
 // Fused finalize (fin.counters != nullptr): the workgroup that completes a row block's last column block (device-scope counter) sums the partials of its 32
-// points in a fixed order (deterministic whoever arrives last), adds the priors and writes loglike / logprior / status -- no separate finalize launch
-// (a launch ramp plus a cold read of the partials, 4.3 us of a 34 us step).  The counter resets itself for the next launch.
+// points in a fixed order (deterministic whoever arrives last), adds the log-priors of the step's prior record (dl_prior.h: written by the theory kernel, the GEMM
+// evaluates no prior) and writes loglike / logprior / status -- no separate finalize launch.  The counter resets itself for the next launch.
 struct DlChi2Fin {
-    int32_t* counters;       // [row blocks], zero before the first launch; nullptr: partials only (dl_finalize_part_kernel follows)
-    const double* theta;     // [M, n_params]
-    const double* priors;    // [n_params, 5]
+    int32_t* counters;       // [row blocks], zero before the first launch; nullptr: partials only (a finalize launch follows)
+    const double* lp_rec;    // [M] prior record: summed log-priors ...
+    const int32_t* flag_rec; // [M] ... and flags (0, 1 out of prior, 3 NaN input)
     double* loglike;         // may be null
     double* logprior;        // may be null
     int32_t* status;         // may be null
-    int32_t n_params, post_mode;
+    int32_t post_mode;
     unsigned long long* stamps;   // DL_CG_STAMPS diagnostics (nullptr in production): 8 slots per workgroup, see dl_fullshape_kernel
     int32_t* ready;          // dl_step_kernel: arrival counters of the row blocks' producers, reset by the last column block of a row block (nullptr otherwise)
 };
@@ -58,10 +58,10 @@ struct DlChi2Panels {
 
 #define DL_CG_STAMP(slot, fn) if (fin.stamps != nullptr && tid == 0) fin.stamps[(size_t)blockIdx.x * 8 + (slot)] = fn();
 // The end of a tile, shared by the two forms of the main loop: in-workgroup reduction of the k-slices of the DL_CG_WAVES waves, bias, square, sum over the 16 columns, partial chi2
-// per row (and the fused finalize of the last-arriving column block when fin.counters is set).  fin_lp / fin_nan: the priors of the row block (lanes 0 .. MT - 1 of wave 0).
+// per row (and the fused finalize of the last-arriving column block when fin.counters is set).
 template <int MT, bool RESID>
 __device__ __forceinline__ void dl_chi2_gemm_finish(dl_cg_double4 acc0, dl_cg_double4 acc1, double bj, double* __restrict__ part, int M, int n_tiles, const DlChi2Fin& fin,
-                                                    double* __restrict__ resid, int64_t ldr, double* lds, int mb, int nt, double fin_lp, int fin_nan) {
+                                                    double* __restrict__ resid, int64_t ldr, double* lds, int mb, int nt) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r16 = lane & 15, g = lane >> 4;
     constexpr int MTILES = MT / 16;
@@ -94,7 +94,8 @@ __device__ __forceinline__ void dl_chi2_gemm_finish(dl_cg_double4 acc0, dl_cg_do
     // Hand-over without cache-maintenance fences: an agent-scope release (buffer_wbl2) walks the XCD's L2 -- 256 of them cost +20 us -- and a full
     // __threadfence() also invalidates it under the workgroups still streaming `power` and W~ (+40 us).  Instead every access to the partials and the counter
     // is itself an agent-scope (sc1) access: the stores above are performed once vmcnt has drained, the counter is a memory-side atomic, the last
-    // arriver's loads bypass non-coherent lines.  One barrier, then wave 0 alone: counter round trip, 8 partial loads, outputs.
+    // arriver's loads bypass non-coherent lines.  One barrier, then wave 0 alone: counter round trip, one round of loads (the partials, lp and flag of the point's
+    // prior record: all requested before the first wait), outputs.
     __asm__ volatile("s_waitcnt vmcnt(0)" : : : "memory");
     __syncthreads();
     if (wave != 0) return;
@@ -106,12 +107,20 @@ __device__ __forceinline__ void dl_chi2_gemm_finish(dl_cg_double4 acc0, dl_cg_do
     if (lane == 0 && fin.ready != nullptr) __hip_atomic_store(fin.ready + mb, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (every consumer of the row block is past its wait)
     const int row = m0 + lane;
     if (lane < MT && row < M) {
+        const double lp = __hip_atomic_load(fin.lp_rec + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int fin_flag = __hip_atomic_load(fin.flag_rec + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         double chi2 = 0.;
-        for (int t = 0; t < n_tiles; ++t) chi2 += __hip_atomic_load(part + (size_t)row * n_tiles + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // fixed order
+        for (int t0 = 0; t0 < n_tiles; t0 += 16) {   // fixed order, from zero: the sum of dl_chi2_of_parts (lanes beyond the count re-read the last element and add nothing)
+            double v[16];
+#pragma unroll
+            for (int t = 0; t < 16; ++t) v[t] = __hip_atomic_load(part + (size_t)row * n_tiles + (t0 + t < n_tiles ? t0 + t : n_tiles - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int t = 0; t < 16; ++t) chi2 = t0 + t < n_tiles ? chi2 + v[t] : chi2;
+        }
         const double inf = __builtin_huge_val();
-        const double lp = fin_lp, ll = -0.5 * chi2;
+        const double ll = -0.5 * chi2;
         int st = 0;                    // DL_STATUS_OK
-        if (fin_nan) st = 3;           // DL_STATUS_NAN_INPUT
+        if (fin_flag == 3) st = 3;     // DL_STATUS_NAN_INPUT
         else if (lp == -inf) st = 1;   // DL_STATUS_OUT_OF_PRIOR
         else if (!(ll == ll) || ll == inf || ll == -inf) st = 2;   // DL_STATUS_NONFINITE
         if (fin.loglike) fin.loglike[row] = fin.post_mode ? (st == 0 ? ll + lp : -inf) : ll;
@@ -164,22 +173,6 @@ __device__ __forceinline__ void dl_chi2_gemm_tile(const double* __restrict__ A, 
     // prologue: panels 0 and 1 requested; panel 0 landed (counted wait: the pieces of panel 1 may still fly) and visible (barrier)
     wait();
     if (DO_LOAD) { DL_CG_DMA(0) if (n_panels > 1) { DL_CG_DMA(1) } }
-    // fused finalize: the priors depend on theta only -- lanes 0-31 of wave 0 evaluate them for the 32 points of the row block now, while the first panels
-    // are in flight (whichever column block arrives last will need them; two registers are carried through the main loop)
-    double fin_lp = 0.;
-    int fin_nan = 0;
-    if (fin.counters != nullptr && wave == 0 && lane < MT && m0 + lane < M) {
-        const double inf = __builtin_huge_val();
-        for (int p = 0; p < fin.n_params; ++p) {
-            double x = fin.theta[(size_t)(m0 + lane) * fin.n_params + p];
-            const double* pr = fin.priors + 5 * p;
-            if (x != x) fin_nan = 1;
-            bool isin = (pr[1] <= x) && (x <= pr[2]);
-            double v = 0.;
-            if (pr[0] == 1.) { double t = x - pr[3]; v = -0.5 * (t * t) / (pr[4] * pr[4]); }   // parameter.py:2007
-            fin_lp += isin ? v : -inf;
-        }
-    }
     if (n_panels > 1) __asm__ volatile("s_waitcnt vmcnt(%0)" : : "n"(VPT) : "memory");
     else __asm__ volatile("s_waitcnt vmcnt(0)" : : : "memory");
     __builtin_amdgcn_s_barrier();
@@ -225,7 +218,7 @@ __device__ __forceinline__ void dl_chi2_gemm_tile(const double* __restrict__ A, 
 #undef DL_CG_MULTIPLY
 #undef DL_CG_MULTIPLY_LIM
 #undef DL_CG_DMA
-    dl_chi2_gemm_finish<MT, RESID>(acc0, acc1, bj, part, M, n_tiles, fin, resid, ldr, lds, mb, nt, fin_lp, fin_nan);
+    dl_chi2_gemm_finish<MT, RESID>(acc0, acc1, bj, part, M, n_tiles, fin, resid, ldr, lds, mb, nt);
 }
 
 // Round 6: the same tile with the B OPERAND OF THE WHOLE TILE IN REGISTERS.  W~ is constant: dl_create lays it out in MFMA fragment order, wfrag [N_pad / 16][K_pad / 4][64]
@@ -277,20 +270,6 @@ __device__ __forceinline__ void dl_chi2_gemm_tile_bf(const double* __restrict__ 
     dl_cg_double4 acc0 = {0., 0., 0., 0.}, acc1 = {0., 0., 0., 0.};
     const double* la = lds + r16 * DL_CG_LD + g;
     if (DO_LOAD) { DL_CG_DMA_A(0) if (n_panels > 1) { DL_CG_DMA_A(1) } }
-    double fin_lp = 0.;
-    int fin_nan = 0;
-    if (fin.counters != nullptr && wave == 0 && lane < MT && m0 + lane < M) {     // (fused finalize: the priors of the row block while the first panels fly)
-        const double inf = __builtin_huge_val();
-        for (int p = 0; p < fin.n_params; ++p) {
-            double x = fin.theta[(size_t)(m0 + lane) * fin.n_params + p];
-            const double* pr = fin.priors + 5 * p;
-            if (x != x) fin_nan = 1;
-            bool isin = (pr[1] <= x) && (x <= pr[2]);
-            double v = 0.;
-            if (pr[0] == 1.) { double t = x - pr[3]; v = -0.5 * (t * t) / (pr[4] * pr[4]); }   // parameter.py:2007
-            fin_lp += isin ? v : -inf;
-        }
-    }
     // panel 0 landed (counted wait: the pieces of panel 1 may still fly; B was requested before either: it is back as well) and visible (barrier)
     if (n_panels > 1) __asm__ volatile("s_waitcnt vmcnt(%0)" : : "n"(VPT) : "memory");
     else __asm__ volatile("s_waitcnt vmcnt(0)" : : : "memory");
@@ -323,7 +302,7 @@ __device__ __forceinline__ void dl_chi2_gemm_tile_bf(const double* __restrict__ 
         }
     }
 #undef DL_CG_DMA_A
-    dl_chi2_gemm_finish<MT, RESID>(acc0, acc1, bj, part, M, n_tiles, fin, resid, ldr, lds, mb, nt, fin_lp, fin_nan);
+    dl_chi2_gemm_finish<MT, RESID>(acc0, acc1, bj, part, M, n_tiles, fin, resid, ldr, lds, mb, nt);
 }
 
 template <bool DO_LOAD, bool DO_MMA, int MT = DL_CG_M, bool RESID = false>

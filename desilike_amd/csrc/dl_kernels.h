@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "dl_fullshape.h"
+#include "dl_prior.h"
 
 // Kernel-interval measurement (dl_profile_*): when dl_eval_* sets these events around a launcher, the kernel is launched with hipExtLaunchKernelGGL, which
 // attaches them to the dispatch packet itself -- start / stop are the packet's own timestamps (what rocprofv3 --kernel-trace reads), no barrier packets
@@ -29,6 +30,8 @@ struct DlOptions {
     bool no_emu_fused, no_gram_epilogue, step_kernel, chi2_fused, no_chi2_big;   // DL_NO_EMU_FUSED, DL_NO_GRAM_EPILOGUE, DL_STEP_KERNEL, DL_CHI2_FUSED, DL_NO_CHI2_BIG (dl_api.hip)
     bool fs_no_moments;   // DL_FS_NO_MOMENTS=1: the fast theory kernels on their interval-polynomial path (polynomial stage, output tile, knot loop without prefetch) where
                           // the moment form would apply (DlObsDev::moment_form; A/B measurements and the parity test of the two paths)
+    bool fs_no_prior;     // DL_FS_NO_PRIOR=1: the theory kernel of a plain-likelihood chi2-GEMM step writes no prior record; the finalize evaluates the priors itself
+                          // (dl_finalize_part_kernel: the form of every other caller; A/B measurements and the parity test of the two forms)
     bool fs_mu_prio;      // DL_FS_MU_PRIO=0: the mu wave of the fast theory kernels without its raised priority (on by default: s_setprio 2 from entry to the barrier before the
                           // evaluation phase; A/B measurements)
     int xcd_local;    // DL_XCD_LOCAL: 0 off, 1 chi2 GEMM path (default), 2 also the theory kernel's point order
@@ -44,10 +47,13 @@ const DlOptions& dl_options();
 #define DL_ST_NAN_INPUT 3
 
 // obs_host: HOST array of observables whose pointers already point into device memory (passed by value to the kernel)
-void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* theta, int n_params, int64_t B, double* power, int64_t ld_power, double* tables,
+// Returns whether the prior record (prior_rec, dl_prior.h) was written: by the launch that carries observable 0 when that is a Kaiser / EFT kernel; false: the caller's
+// finalize evaluates the priors itself.
+bool dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* theta, int n_params, int64_t B, double* power, int64_t ld_power, double* tables,
                          int64_t ld_tables, hipStream_t stream, double* feat = nullptr, int64_t feat_ld = 0, int xcd_block = 0,   // xcd_block: rows per row block of the consuming GEMM (0: points in launch order)
                          const DlObsDev* obs_dev = nullptr,    // obs_dev: the same observables as a DEVICE array (enables one launch for all of them)
-                         bool moments = true);                 // moments = false: never the moment form (the gradient entry point: value and gradient from the same interval polynomials)
+                         bool moments = true,                  // moments = false: never the moment form (the gradient entry point: value and gradient from the same interval polynomials)
+                         const DlPriorRec* prior_rec = nullptr);
 // bias is added to rows r with r % bias_period == 0 only (bias_period = 1: every row)
 void dl_launch_window_gemm(const double* A, int64_t lda, const double* Wt, int64_t ldw, const double* bias, double* C, int64_t ldc, int64_t M, int N_valid, int N_pad,
                            int K_pad, int bias_period, hipStream_t stream);
@@ -74,13 +80,16 @@ void dl_launch_window_gemm_tiled(const double* A, int64_t lda, const double* Wt,
 void dl_launch_finalize(const double* dtilde, int64_t ld, int n, int n_slabs, int64_t slab_stride, const double* bias, const double* theta, int n_params,
                         const double* priors, int64_t B, double* loglike, double* logprior, int32_t* status, int post_mode, hipStream_t stream);
 // chi2 GEMM path: part[M, N_pad / 16] = partial chi2 per 16-column block (bias added inside), summed with the priors by dl_launch_finalize_part
-// counters != nullptr ([ceil(M / 32) rounded up to 8] zeroed int32): the finalize (priors, status, outputs) is fused into the GEMM's last-arriving workgroups
+// counters != nullptr ([ceil(M / 32) rounded up to 8] zeroed int32): the finalize (chi2 sum, log-priors of the record, status, outputs) is fused into the GEMM's last-arriving workgroups
 int dl_chi2_gemm_row_tile(int64_t M, int N_pad);   // 32 or 16: rows per workgroup the chi2 GEMM will use for a batch of M points (the theory kernel deals the points to the XCDs accordingly)
 void dl_launch_chi2_gemm(const double* A, int64_t lda, const double* Wt, int64_t ldw, const double* bias, double* part, int64_t M, int N_pad, int K_pad, int32_t* counters,
-                         const double* theta, int n_params, const double* priors, double* loglike, double* logprior, int32_t* status, int post_mode, hipStream_t stream,
+                         const DlPriorRec* rec, double* loglike, double* logprior, int32_t* status, int post_mode, hipStream_t stream,   // rec: the prior record of the step's theory launch (the fused finalize reads it; null with counters == nullptr)
                          const uint8_t* panel_ranges = nullptr, int k_live = 0, double* resid = nullptr, int64_t ldr = 0, const double* wfrag = nullptr);   // wfrag: Wt in MFMA fragment order [N_pad / 16][K_pad / 4][64] (dl_chi2_gemm_tile_bf, taken under DL_CHI2_BFRAG=1 only: the B operand in registers -- measured slower than both operands through LDS); resid [M, ldr]: the residual rows themselves, also written (may be null); panel_ranges [N_pad / 16][2]: 128-wide K panels [lo, hi) with non-zero Wt entries per column block (host array), or null
 void dl_launch_finalize_part(const double* part, int n_tiles, const double* theta, int n_params, const double* priors, int64_t B, double* loglike, double* logprior,
                              int32_t* status, int post_mode, hipStream_t stream);
+// ... with the prior record of the step's theory launch: the chi2 sum, the status and the stores only
+void dl_launch_finalize_rec(const double* part, int n_tiles, const DlPriorRec& rec, int64_t B, double* loglike, double* logprior, int32_t* status, int post_mode,
+                            hipStream_t stream);
 #ifndef DL_FG_NM
 #define DL_FG_NM 19           // bias monomials of the velocileptors table combination
 #define DL_FG_MONO_LD 20      // monomial rows are padded to 20 doubles in the point records
@@ -99,8 +108,8 @@ void dl_launch_emulated_feature(const DlObsDev& obs, const double* theta, int n_
 // contexts at <= 1024 points; dl_step_lds_bytes returns 0 when the configuration is not eligible.  `ready`: [>= B / 32] arrival counters that count up (target = 8 x launch number)
 size_t dl_step_lds_bytes(const DlObsDev& obs, int64_t B, int N_pad);
 void dl_launch_step(const DlObsDev& obs, const double* theta, int n_params, int64_t B, double* power, int64_t ld_power, const double* Wt, int64_t ldw, const double* bias,
-                    double* part, int K_pad, int k_live, int32_t* counters, int32_t* ready, int32_t target, const double* priors, double* loglike, double* logprior, int32_t* status,
-                    int post_mode, hipStream_t stream, const uint8_t* panel_ranges);
+                    double* part, int K_pad, int k_live, int32_t* counters, int32_t* ready, int32_t target, const DlPriorRec& rec, double* loglike, double* logprior, int32_t* status,
+                    int post_mode, hipStream_t stream, const uint8_t* panel_ranges);   // rec: written by the theory part of the launch, read by its fused finalize
 // stacked table engine (obs.eng[0].type == 2: the jaxeffort layout of emulators/conversion.py:44-98; dl_emu_stacked.h): every network of every group by MFMA and the feature
 // GEMM in one launch; gfrag: [N_pad / 16][steps_per_block][64][2] (group by group, k / 8 by k / 8, monomial by monomial)
 bool dl_emulated_stacked_ok(const DlObsDev& obs);

@@ -65,7 +65,7 @@ static void dl_options_read() {
     o.host_mode = std::getenv("DL_HOST_MODE") ? atoi(std::getenv("DL_HOST_MODE")) : -1;
     auto flag = [](const char* name) { const char* v = std::getenv(name); return v != nullptr && atoi(v) != 0; };
     o.no_emu_fused = on("DL_NO_EMU_FUSED"); o.no_gram_epilogue = on("DL_NO_GRAM_EPILOGUE"); o.no_chi2_big = on("DL_NO_CHI2_BIG");
-    o.fs_no_moments = flag("DL_FS_NO_MOMENTS");
+    o.fs_no_moments = flag("DL_FS_NO_MOMENTS"); o.fs_no_prior = flag("DL_FS_NO_PRIOR");
     o.fs_mu_prio = std::getenv("DL_FS_MU_PRIO") ? atoi(std::getenv("DL_FS_MU_PRIO")) != 0 : true;
     o.step_kernel = flag("DL_STEP_KERNEL"); o.chi2_fused = flag("DL_CHI2_FUSED"); o.chi2_bfrag = flag("DL_CHI2_BFRAG");
     o.xcd_local = std::getenv("DL_XCD_LOCAL") ? atoi(std::getenv("DL_XCD_LOCAL")) : 1;
@@ -98,7 +98,8 @@ template <bool FAST, int NL, bool EFT, bool DENSE, bool TH_ROW = false, bool SUB
 __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const double* __restrict__ theta, int n_params, double* __restrict__ power,
                                                   int64_t ld_power, double* __restrict__ tables, int64_t ld_tables, int stop_after, unsigned long long* __restrict__ stamps,
                                                   const double* th_row = nullptr,     // th_row: the point's parameters already in LDS (dl_fullshape_ens_kernel)
-                                                  double* lds_sub = nullptr, int tid_sub = 0, int b_sub = 0) {
+                                                  double* lds_sub = nullptr, int tid_sub = 0, int b_sub = 0,
+                                                  const DlPriorRec& rec = DlPriorRec{}) {   // rec.lp != nullptr: observable 0's workgroup also writes the point's prior record
     extern __shared__ __attribute__((aligned(16))) double lds_wg[];
     double* lds = SUB ? lds_sub : lds_wg;
     // Workgroups are dealt round-robin to the 8 XCDs; the GEMM that follows runs row block mb (xblk = 32 or 64 points) on XCD mb % 8.  With xblk > 0 the points are dealt
@@ -123,6 +124,12 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
     const bool direct = MOM && dl_fs_mom_direct(o);
     const double* th = TH_ROW ? th_row : theta + (size_t)b * n_params;
     if (stop_after == -1) return;  // stop_after != 0: timing diagnostics only (DL_FS_STOP), outputs are then incomplete
+    // Prior record (dl_prior.h): the last spline wave (wave NT / 64 - 2; the strided knot loops leave it the short share, and the phase lasts as long as the per-mu chain of
+    // the wave behind it: DL_FS_STAMPS, round 8) requests the prior rows and the parameter values with the kernel's first loads and is done with them before its knots.
+    // Uniform branch: a null pointer costs one scalar compare; callers that pass no record compile none of it.
+    // Moment form: the record waits for the end fix-up phase instead, where only wave 0 and the mu wave have work and wave 1 stands at the barrier.
+    const bool rec_on = !TH_ROW && rec.lp != nullptr && blockIdx.y == 0, rec_late = FAST && MOM && !o.fixed_spline;
+    if (rec_on && !rec_late && __builtin_amdgcn_readfirstlane(tid >> 6) == NT / 64 - 2) dl_prior_record(rec, th, n_params, tid & 63, b);
     // constants of the later phases are requested now: their round trip hides behind phase 0/1
     double lk_pref[DL_P3_PREF];
 #pragma unroll
@@ -174,7 +181,10 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
             if (mu_wave) {
                 if (mu_lane) dl_fs_mu_partC(o, s, m, c, false);
                 if (scalar_lane) dl_fs_scalars(o, th, s, c, false);
-            } else if (MOM) { if (tid < 64) dl_fs_mom_fixup(tid, o, s); }
+            } else if (MOM) {
+                if (tid < 64) dl_fs_mom_fixup(tid, o, s);
+                else if (rec_on && __builtin_amdgcn_readfirstlane(tid >> 6) == 1) dl_prior_record(rec, th, n_params, tid & 63, b);
+            }
             else dl_fs_phase2d_toep(tid, KT, o, s, dlt_pref);
             __syncthreads();
             DL_STAMP(3)
@@ -233,9 +243,10 @@ __device__ __forceinline__ void dl_fullshape_body(const DlObsDev& o, const doubl
 
 template <bool FAST, int NL, bool EFT, bool DENSE = false, bool MOM = false>
 __global__ __launch_bounds__(DL_FS_THREADS, DENSE ? 5 : 4) void dl_fullshape_kernel(const DlObsDev o, const double* __restrict__ theta, int n_params, double* __restrict__ power,
-                                                                     int64_t ld_power, double* __restrict__ tables, int64_t ld_tables, int stop_after, unsigned long long* __restrict__ stamps) {
+                                                                     int64_t ld_power, double* __restrict__ tables, int64_t ld_tables, int stop_after, unsigned long long* __restrict__ stamps,
+                                                                     const DlPriorRec rec) {
     dl_obs_prefetch((const void*)__builtin_amdgcn_kernarg_segment_ptr());
-    dl_fullshape_body<FAST, NL, EFT, DENSE, false, false, DL_FS_THREADS, MOM>(o, theta, n_params, power, ld_power, tables, ld_tables, stop_after, stamps);
+    dl_fullshape_body<FAST, NL, EFT, DENSE, false, false, DL_FS_THREADS, MOM>(o, theta, n_params, power, ld_power, tables, ld_tables, stop_after, stamps, nullptr, nullptr, 0, 0, rec);
 }
 
 // The moment form applies (kernels of one launch share it: every observable must qualify); DL_FS_NO_MOMENTS selects the interval-polynomial path everywhere
@@ -252,9 +263,9 @@ static size_t dl_fs_fast_shared_bytes(const DlObsDev& oh, bool mom) { return (mo
 // profiles/r06d_wide_theory.txt): 64 - 256 points 18.0 - 18.2 -> 17.3 - 17.6 us per step; 512 points 19.05 -> 19.2, 1024 points 23.6 -> 28.6 us (four 512-thread workgroups do not fit a CU).
 template <int NL, bool MOM = false>
 __global__ __launch_bounds__(512, 2) void dl_fullshape_wide_kernel(const DlObsDev o, const double* __restrict__ theta, int n_params, double* __restrict__ power,
-                                                                 int64_t ld_power, int stop_after, unsigned long long* __restrict__ stamps) {
+                                                                 int64_t ld_power, int stop_after, unsigned long long* __restrict__ stamps, const DlPriorRec rec) {
     dl_obs_prefetch((const void*)__builtin_amdgcn_kernarg_segment_ptr());
-    dl_fullshape_body<true, NL, false, false, false, false, 512, MOM>(o, theta, n_params, power, ld_power, nullptr, 0, stop_after, stamps);
+    dl_fullshape_body<true, NL, false, false, false, false, 512, MOM>(o, theta, n_params, power, ld_power, nullptr, 0, stop_after, stamps, nullptr, nullptr, 0, 0, rec);
 }
 
 // ---- scale-dependent bias from local primordial non-Gaussianity (theory kind 5; primordial_non_gaussianity.py:75-112) ---------------------------------------------
@@ -312,8 +323,8 @@ __global__ __launch_bounds__(DL_FS_THREADS, 2) void dl_png_kernel(DlObsDev o, co
 // bound (two tracers x 256 walkers: 2 x 8.6 us -> one launch).
 template <bool FAST, int NL, bool EFT, bool DENSE = false, bool MOM = false>
 __global__ __launch_bounds__(DL_FS_THREADS, DENSE ? 5 : 4) void dl_fullshape_multi_kernel(const DlObsDev* __restrict__ obs, const double* __restrict__ theta, int n_params,
-                                                                           double* __restrict__ power, int64_t ld_power, int stop_after) {
-    dl_fullshape_body<FAST, NL, EFT, DENSE, false, false, DL_FS_THREADS, MOM>(obs[blockIdx.y], theta, n_params, power, ld_power, nullptr, 0, stop_after, nullptr);
+                                                                           double* __restrict__ power, int64_t ld_power, int stop_after, const DlPriorRec rec) {
+    dl_fullshape_body<FAST, NL, EFT, DENSE, false, false, DL_FS_THREADS, MOM>(obs[blockIdx.y], theta, n_params, power, ld_power, nullptr, 0, stop_after, nullptr, nullptr, nullptr, 0, 0, rec);
 }
 
 // ---- folded ensemble update (dl_ens_fold.h): the workgroup derives the proposal it evaluates --------------------------------------------------------------------
@@ -700,10 +711,14 @@ static void dl_launch_ws_templates(const DlObsDev* obs_host, int n_obs, const do
     }
 }
 
-void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* theta, int n_params, int64_t B, double* power, int64_t ld_power, double* tables,
-                         int64_t ld_tables, hipStream_t stream, double* feat, int64_t feat_ld, int xcd_block, const DlObsDev* obs_dev, bool moments) {
+bool dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* theta, int n_params, int64_t B, double* power, int64_t ld_power, double* tables,
+                         int64_t ld_tables, hipStream_t stream, double* feat, int64_t feat_ld, int xcd_block, const DlObsDev* obs_dev, bool moments, const DlPriorRec* prior_rec) {
     dl_launch_ws_templates(obs_host, n_obs, theta, n_params, B, stream);   // (before any theory kernel, merged launch included: their knot phase copies the rows)
     static const int stop_after = getenv("DL_FS_STOP") ? atoi(getenv("DL_FS_STOP")) : 0;   // per-phase timing diagnostics
+    // the prior record is written by the launch that carries observable 0, when that launch is one of the Kaiser / EFT kernels below and runs to its end
+    const bool rec_ok = prior_rec != nullptr && prior_rec->lp != nullptr && stop_after == 0 && obs_host[0].templ != 5;
+    const DlPriorRec rec_on = rec_ok ? *prior_rec : DlPriorRec{};
+    bool rec_written = false;
     // DL_FS_STAMPS=<file>: in-kernel timestamps of the launches with B >= 256 are appended to <file> as text (synchronises: diagnostics only)
     static const char* stamp_file = getenv("DL_FS_STAMPS");
     static unsigned long long* stamps_dev = nullptr;
@@ -728,11 +743,11 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
             auto launch = [&](auto kernel) {
                 if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
                 const int flags = dl_fs_launch_flags((xcd_block > 0 && B % (8 * xcd_block) == 0) ? xcd_block : 0, 0);
-                DL_LAUNCH(kernel, dim3((unsigned)B, (unsigned)n_obs), dim3(DL_FS_THREADS), shmem, stream, obs_dev, theta, n_params, power, ld_power, flags);
+                DL_LAUNCH(kernel, dim3((unsigned)B, (unsigned)n_obs), dim3(DL_FS_THREADS), shmem, stream, obs_dev, theta, n_params, power, ld_power, flags, rec_on);
             };
             if (nl3) { if (dense) launch(dl_fullshape_multi_kernel<true, 3, false, true>); else if (mom) launch(dl_fullshape_multi_kernel<true, 3, false, false, true>); else launch(dl_fullshape_multi_kernel<true, 3, false>); }
             else { if (dense) launch(dl_fullshape_multi_kernel<true, 5, false, true>); else if (mom) launch(dl_fullshape_multi_kernel<true, 5, false, false, true>); else launch(dl_fullshape_multi_kernel<true, 5, false>); }
-            return;
+            return rec_ok;
         }
     }
     for (int i = 0; i < n_obs; ++i) {  // one launch per observable (1-2 in practice)
@@ -778,6 +793,8 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
             continue;
         }
         const DlObsDev& oh = obs_host[i];
+        const DlPriorRec rec = i == 0 ? rec_on : DlPriorRec{};
+        rec_written = rec_written || (i == 0 && rec_ok);
         const bool generic = tables || !oh.uniform_knots || !(oh.toeplitz || oh.fixed_spline);
         static const int64_t dense_min = getenv("DL_FS_DENSE_MIN") ? atoll(getenv("DL_FS_DENSE_MIN")) : 4096;   // batches above: the 5-workgroups-per-CU variant
         bool nl3 = oh.n_ell <= 3, eft = oh.n_ct > 0 || oh.n_sn > 0;
@@ -788,7 +805,7 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
         auto launch = [&](auto kernel) {
             if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);  // e.g. 2000-knot BAO tables
             const int flags = dl_fs_launch_flags((xcd_block > 0 && B % (8 * xcd_block) == 0) ? xcd_block : 0, stop_after);
-            DL_LAUNCH(kernel, dim3((unsigned)B), dim3(DL_FS_THREADS), shmem, stream, obs_host[i], theta, n_params, power, ld_power, tables, ld_tables, flags, stamps);
+            DL_LAUNCH(kernel, dim3((unsigned)B), dim3(DL_FS_THREADS), shmem, stream, obs_host[i], theta, n_params, power, ld_power, tables, ld_tables, flags, stamps, rec);
             if (stamps) {
                 (void)hipStreamSynchronize(stream);
                 std::vector<unsigned long long> h((size_t)B * DL_FS_STAMP_SLOTS);
@@ -804,7 +821,7 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
             auto launch_wide = [&](auto kernel) {
                 if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
                 const int flags = dl_fs_launch_flags((xcd_block > 0 && B % (8 * xcd_block) == 0) ? xcd_block : 0, stop_after);
-                DL_LAUNCH(kernel, dim3((unsigned)B), dim3(512), shmem, stream, obs_host[i], theta, n_params, power, ld_power, flags, stamps);
+                DL_LAUNCH(kernel, dim3((unsigned)B), dim3(512), shmem, stream, obs_host[i], theta, n_params, power, ld_power, flags, stamps, rec);
             };
             if (nl3) { if (mom) launch_wide(dl_fullshape_wide_kernel<3, true>); else launch_wide(dl_fullshape_wide_kernel<3>); }
             else { if (mom) launch_wide(dl_fullshape_wide_kernel<5, true>); else launch_wide(dl_fullshape_wide_kernel<5>); }
@@ -816,6 +833,7 @@ void dl_launch_fullshape(const DlObsDev* obs_host, int n_obs, const double* thet
         else if (!eft) { if (B > dense_min) launch(dl_fullshape_kernel<true, 5, false, true>); else if (mom) launch(dl_fullshape_kernel<true, 5, false, false, true>); else launch(dl_fullshape_kernel<true, 5, false>); }
         else launch(dl_fullshape_kernel<true, 5, true>);
     }
+    return rec_written;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1266,8 +1284,9 @@ int dl_chi2_gemm_row_tile(int64_t M, int N_pad) {
 }
 
 void dl_launch_chi2_gemm(const double* A, int64_t lda, const double* Wt, int64_t ldw, const double* bias, double* part, int64_t M, int N_pad, int K_pad, int32_t* counters,
-                         const double* theta, int n_params, const double* priors, double* loglike, double* logprior, int32_t* status, int post_mode, hipStream_t stream,
+                         const DlPriorRec* rec, double* loglike, double* logprior, int32_t* status, int post_mode, hipStream_t stream,
                          const uint8_t* panel_ranges, int k_live, double* resid, int64_t ldr, const double* wfrag) {
+    if (rec == nullptr || rec->lp == nullptr) counters = nullptr;   // (no fused finalize without the record)
     const int n_tiles = N_pad / DL_CG_N;
     const int mt = counters == nullptr ? dl_chi2_gemm_row_tile(M, N_pad) : DL_CG_M;   // (the experimental fused finalize counts 32-row blocks)
     const int64_t mblocks = (M + mt - 1) / mt;
@@ -1281,8 +1300,8 @@ void dl_launch_chi2_gemm(const double* A, int64_t lda, const double* Wt, int64_t
         optin = true;
     }
     DlChi2Fin fin;
-    fin.counters = counters; fin.theta = theta; fin.priors = priors; fin.loglike = loglike; fin.logprior = logprior; fin.status = status;
-    fin.n_params = n_params; fin.post_mode = post_mode; fin.ready = nullptr;
+    fin.counters = counters; fin.lp_rec = counters ? rec->lp : nullptr; fin.flag_rec = counters ? rec->flag : nullptr; fin.loglike = loglike; fin.logprior = logprior; fin.status = status;
+    fin.post_mode = post_mode; fin.ready = nullptr;
     static const char* stamp_file = getenv("DL_CG_STAMPS");   // diagnostics: in-kernel timestamps of launches 30..33 appended to the file (synchronises)
     static unsigned long long* stamps_dev = nullptr;
     static int stamp_launches = 0;
@@ -1344,14 +1363,14 @@ void dl_launch_chi2_gemm(const double* A, int64_t lda, const double* Wt, int64_t
 template <int NL>
 __global__ __launch_bounds__(1024) void dl_step_kernel(const DlObsDev o, const double* __restrict__ theta, int n_params, double* __restrict__ power, int64_t ld_power,
                                                        const double* __restrict__ Wt, int64_t ldw, const double* __restrict__ bias, double* __restrict__ part, int M, int K_pad,
-                                                       DlChi2Fin fin, DlChi2Panels panels, int k_live, int32_t* __restrict__ ready, int32_t target, int lds_per_point) {
+                                                       DlChi2Fin fin, DlChi2Panels panels, int k_live, int32_t* __restrict__ ready, int32_t target, int lds_per_point, const DlPriorRec rec) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int L = blockIdx.x, xcd = L & 7, j = L >> 3;
     const int q = j >> 3, c = j & 7, mb = xcd + 8 * q;
     const int sub = threadIdx.x >> 8, tid = threadIdx.x & 255;
     unsigned long long* st = fin.stamps != nullptr ? fin.stamps + (size_t)blockIdx.x * 8 : nullptr;   // DL_STEP_STAMPS: 0 entry, 1 theory done, 2 published, 3 rows ready, 4 GEMM + finalize done
     if (st != nullptr && threadIdx.x == 0) { st[0] = __builtin_amdgcn_s_memtime(); st[6] = __builtin_amdgcn_s_memrealtime(); }
-    dl_fullshape_body<true, NL, false, false, false, true>(o, theta, n_params, power, ld_power, nullptr, 0, 0, nullptr, nullptr, lds + (size_t)sub * lds_per_point, tid, 32 * mb + 4 * c + sub);
+    dl_fullshape_body<true, NL, false, false, false, true>(o, theta, n_params, power, ld_power, nullptr, 0, 0, nullptr, nullptr, lds + (size_t)sub * lds_per_point, tid, 32 * mb + 4 * c + sub, rec);
     if (st != nullptr && threadIdx.x == 0) st[1] = __builtin_amdgcn_s_memtime();
     // the rows of this workgroup's four points are performed at agent scope once every wave's stores have drained; then they are published
     __asm__ volatile("s_waitcnt vmcnt(0)" : : : "memory");
@@ -1384,7 +1403,7 @@ size_t dl_step_lds_bytes(const DlObsDev& oh, int64_t B, int N_pad) {
 }
 
 void dl_launch_step(const DlObsDev& oh, const double* theta, int n_params, int64_t B, double* power, int64_t ld_power, const double* Wt, int64_t ldw, const double* bias,
-                    double* part, int K_pad, int k_live, int32_t* counters, int32_t* ready, int32_t target, const double* priors, double* loglike, double* logprior, int32_t* status,
+                    double* part, int K_pad, int k_live, int32_t* counters, int32_t* ready, int32_t target, const DlPriorRec& rec, double* loglike, double* logprior, int32_t* status,
                     int post_mode, hipStream_t stream, const uint8_t* panel_ranges) {
     DlChi2Panels panels;
     std::memset(&panels, 0, sizeof(panels));
@@ -1394,8 +1413,8 @@ void dl_launch_step(const DlObsDev& oh, const double* theta, int n_params, int64
     static bool optin = false;
     if (!optin) { (void)hipFuncSetAttribute((const void*)dl_step_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); optin = true; }
     DlChi2Fin fin;
-    fin.counters = counters; fin.theta = theta; fin.priors = priors; fin.loglike = loglike; fin.logprior = logprior; fin.status = status;
-    fin.n_params = n_params; fin.post_mode = post_mode; fin.ready = ready;
+    fin.counters = counters; fin.lp_rec = rec.lp; fin.flag_rec = rec.flag; fin.loglike = loglike; fin.logprior = logprior; fin.status = status;
+    fin.post_mode = post_mode; fin.ready = ready;
     const unsigned grid = (unsigned)(B / 4);
     static const char* stamp_file = getenv("DL_STEP_STAMPS");   // diagnostics: in-kernel timestamps of launches 30..33 appended to the file (synchronises)
     static unsigned long long* stamps_dev = nullptr;
@@ -1405,7 +1424,7 @@ void dl_launch_step(const DlObsDev& oh, const double* theta, int n_params, int64
     if (stamp_file) stamp_launches++;
     if (fin.stamps) (void)hipMemsetAsync(fin.stamps, 0, (size_t)256 * 8 * sizeof(unsigned long long), stream);
     DL_LAUNCH(dl_step_kernel<3>, dim3(grid), dim3(1024), shm, stream, oh, theta, n_params, power, ld_power, Wt, ldw, bias, part, (int)B, K_pad, fin, panels, k_live > 0 ? k_live : K_pad,
-              ready, target, (int)per_point);
+              ready, target, (int)per_point, rec);
     if (fin.stamps) {
         (void)hipStreamSynchronize(stream);
         std::vector<unsigned long long> h((size_t)grid * 8);
@@ -1454,6 +1473,31 @@ void dl_launch_finalize_part(const double* part, int n_tiles, const double* thet
     const size_t shm = (size_t)5 * n_params * sizeof(double);
     if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)dl_finalize_part_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     DL_LAUNCH(dl_finalize_part_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), shm, stream, part, n_tiles, theta, n_params, priors, B, loglike, logprior, status, post_mode);
+}
+
+// The finalize behind a theory launch that wrote the prior record (DlPriorRec): no prior table, no LDS stage, no barrier -- the partial sums, lp and flag of the point are
+// requested together, then the fixed-order sum (dl_chi2_of_parts), the status rules and the stores.  (Eight lanes per point -- a point's 64-byte row of partials as one
+// coalesced line, eight times as many CUs, the same bits -- was measured slower, 22.92 against 22.79 us per 1024-point step, and taken out: docs/EXPERIMENTS.md.)
+__global__ __launch_bounds__(64) void dl_finalize_rec_kernel(const double* __restrict__ part, int n_tiles, const double* __restrict__ lp_rec, const int32_t* __restrict__ flag_rec,
+                                                              int64_t B, double* __restrict__ loglike, double* __restrict__ logprior, int32_t* __restrict__ status, int post_mode) {
+    dl_kernarg_prefetch<96>();
+    const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const double lp = lp_rec[b];
+    const int fl = flag_rec[b];
+    const double chi2 = dl_chi2_of_parts(part + (size_t)b * n_tiles, n_tiles);
+    const double inf = __builtin_huge_val();
+    double ll;
+    int st;
+    dl_finalize_status(chi2, lp, fl == DL_ST_NAN_INPUT, ll, st);
+    if (loglike) loglike[b] = post_mode ? (st == DL_ST_OK ? ll + lp : -inf) : ll;
+    if (logprior) logprior[b] = lp;
+    if (status) status[b] = st;
+}
+
+void dl_launch_finalize_rec(const double* part, int n_tiles, const DlPriorRec& rec, int64_t B, double* loglike, double* logprior, int32_t* status, int post_mode,
+                            hipStream_t stream) {
+    DL_LAUNCH(dl_finalize_rec_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, part, n_tiles, (const double*)rec.lp, (const int32_t*)rec.flag, B, loglike, logprior, status, post_mode);
 }
 
 // ---- lane-parallel dense algebra for the <= 15 x 15 systems of the marginalised finalize: lane i owns row i in registers, rows are exchanged with

@@ -8,6 +8,7 @@
 //   -inf outside the limits or the support.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 
 #define DL_PRIOR_MAX_KIND 9
 
@@ -37,4 +38,39 @@ __device__ __forceinline__ double dl_prior_logpdf(const double* __restrict__ pr,
     if (kind == 1.) { const double t = x - loc; v = -0.5 * (t * t) / (scale * scale); }   // parameter.py:2007
     else if (kind >= 2.) v = dl_prior_family((int)kind, (x - loc) / scale);
     return isin ? v : -inf;
+}
+
+// Prior record of a point: the part of the result that depends on theta alone, written by the theory kernel that opens a plain-likelihood chi2-GEMM step
+// (dl_fullshape_body) so that the finalize behind the GEMM is left with the chi2 sum.  lp [B]: summed log-prior; flag [B]: 0, 1 (out of prior), 3 (NaN input) --
+// the values of dl_finalize_status.  lp == nullptr: no record (every other caller of the theory kernels).
+struct DlPriorRec {
+    const double* priors = nullptr;   // [n_params, 5]
+    double* lp = nullptr;
+    int32_t* flag = nullptr;
+};
+
+// The record of point b by ONE wave.  Lane p evaluates parameter p (one round of loads: its prior row and its value, requested together), then the terms are added
+// in parameter order from zero -- the order of dl_finalize_from_chi2, term by term through v_readlane (uniform lane index): the sum has that loop's bits.
+__device__ __forceinline__ void dl_prior_record(const DlPriorRec& rec, const double* __restrict__ th, int n_params, int lane, int64_t b) {
+    const double inf = __builtin_huge_val();
+    double lp = 0.;
+    bool nan_in = false;
+    for (int p0 = 0; p0 < n_params; p0 += 64) {
+        const bool live = p0 + lane < n_params;
+        const int p = live ? p0 + lane : n_params - 1;
+        double pr[5];
+#pragma unroll
+        for (int c = 0; c < 5; ++c) pr[c] = rec.priors[5 * p + c];
+        const double x = th[p];
+        const double v = dl_prior_logpdf(pr, x);
+        nan_in = nan_in || __ballot(live && x != x) != 0;
+        const int n = n_params - p0 < 64 ? n_params - p0 : 64;
+        const int v_lo = __double2loint(v), v_hi = __double2hiint(v);
+        for (int q = 0; q < n; ++q) lp += __hiloint2double(__builtin_amdgcn_readlane(v_hi, q), __builtin_amdgcn_readlane(v_lo, q));
+    }
+    if (lane == 0) {
+        // agent-scope (write-through) stores, as the theory rows: a consumer inside the same launch (dl_step_kernel) reads them after the row block's hand-over
+        __hip_atomic_store(rec.lp + b, lp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(rec.flag + b, nan_in ? 3 : (lp == -inf ? 1 : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }

@@ -296,6 +296,8 @@ int  dl_profile_read(dl_ctx* ctx, double* ms, int32_t n);
  *     largest value, not bit for bit -- tests/test_gpu_fullshape_moments.py compares the two)
  *     DL_FS_MU_PRIO=0 (the fast full-shape kernels without the raised priority of the wave that runs the per-mu chain: a scheduling hint, bit-identical results --
  *     tests/test_gpu_fullshape_balance.py)
+ *     DL_FS_NO_PRIOR=1 (plain-likelihood chi2-GEMM step: the theory kernel writes no prior record, the finalize behind the GEMM evaluates the priors itself -- the form of every
+ *     other path; DL_CHI2_FUSED / DL_STEP_KERNEL then fall back to the separate launches): bit-identical results -- tests/test_gpu_prior_in_theory.py
  *   diagnostics (in-kernel time stamps written to the named file, per-phase early exits; they synchronise: never set in production):
  *     DL_FS_STAMPS, DL_FS_STOP, DL_CG_STAMPS, DL_EF_STAMPS, DL_FM_STAMPS, DL_STK_STAMPS, DL_STEP_STAMPS, DL_ENS_STAMPS, DL_ENS_FOLD_STAMPS
  *   environment of the collectives: DL_RCCL_PATH, DL_COMM_TIMEOUT (desilike_amd/parallel.py, bench.py) */

@@ -31,7 +31,8 @@ def shifted_wiggles(c, baoshift):
 
 
 def pk_dd(c, baoshift):
-    """power_template.py:492."""
+    """power_template.py:492; without the phase-shift keys (``BAOPowerSpectrumTemplate``): the fiducial spectrum itself."""
+    if 'ps_k' not in c: return c['pk_dd_fid']
     return c['pknow_dd_fid'] + shifted_wiggles(c, baoshift)
 
 

@@ -519,7 +519,9 @@ static int64_t tns_pass_points(const DlTnsDev& t) {
     return pts < DL_TNS_PTS ? DL_TNS_PTS : (pts > 8192 ? 8192 : pts);
 }
 
-static bool tns_run_loop(DlTnsPlan* plan, const DlObsDev& obs, const double* theta, int n_params, int64_t nb, hipStream_t stream) {
+// nb: the points of this pass; nb_call: the points of the call's FIRST pass -- the variant is chosen once per call, from them: a point's sums then do not depend on the pass
+// it falls into (the variants add in different orders; a remainder pass of one point used to take another one than the 8192 points before it)
+static bool tns_run_loop(DlTnsPlan* plan, const DlObsDev& obs, const double* theta, int n_params, int64_t nb, int64_t nb_call, hipStream_t stream) {
     const DlTnsDev& t = plan->dev;
     const int64_t ldp = (nb + DL_TNS_PTS - 1) / DL_TNS_PTS * DL_TNS_PTS;
     if (!tns_reserve(plan, ldp)) { dl_set_last_error("tns: workspace allocation failed"); return false; }
@@ -536,9 +538,10 @@ static bool tns_run_loop(DlTnsPlan* plan, const DlObsDev& obs, const double* the
     if (n_cu == 0) { int dev = 0; hipDeviceProp_t prop; n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256; }
     int w_best = 8;
     double t_best = 1e300;
+    const int64_t tiles_call = (nb_call + DL_TNS_PTS - 1) / DL_TNS_PTS;
     for (int w = 8; w >= 1; w /= 2) {
         const int kpw = DL_TNS_WAVES / w;
-        const int64_t wgs = (int64_t)((t.n11 + kpw - 1) / kpw) * n_tiles, rounds = (wgs + n_cu - 1) / n_cu;
+        const int64_t wgs = (int64_t)((t.n11 + kpw - 1) / kpw) * tiles_call, rounds = (wgs + n_cu - 1) / n_cu;
         const double cost = (double)rounds * (20. + 55. * (8. / w) * ((double)t.Kp / 5008.));
         if (cost < t_best) { t_best = cost; w_best = w; }
     }
@@ -571,7 +574,7 @@ void dl_launch_tns(const DlObsDev& obs, const double* theta, int n_params, int64
     for (int64_t b0 = 0; b0 < B; b0 += pass) {
         const int64_t nb = std::min(pass, B - b0);
         const double* th = theta + (size_t)b0 * n_params;
-        if (!tns_run_loop(plan, obs, th, n_params, nb, stream)) return;
+        if (!tns_run_loop(plan, obs, th, n_params, nb, std::min(pass, B), stream)) return;
         double* prow = power + (size_t)b0 * (1 + obs.n_var) * ld_power;
         // points per workgroup: as many polynomials as the 16-row tile holds when the batch still gives every CU two workgroups, one point otherwise
         int ppw = nb >= 1536 ? 16 / nq : nb >= 1024 ? 2 : 1;
@@ -591,7 +594,7 @@ int dl_tns_tables(const DlObsDev& obs, const double* theta, int n_params, int64_
     const int64_t pass = tns_pass_points(t);
     for (int64_t b0 = 0; b0 < B; b0 += pass) {
         const int64_t nb = std::min(pass, B - b0);
-        if (!tns_run_loop(plan, obs, theta + (size_t)b0 * n_params, n_params, nb, stream)) return 1;
+        if (!tns_run_loop(plan, obs, theta + (size_t)b0 * n_params, n_params, nb, std::min(pass, B), stream)) return 1;
         const int64_t total = nb * DL_TNS_NTAB * t.n11;
         hipLaunchKernelGGL(dl_tns_tables_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, t, plan->tables, plan->qq, plan->ldp, nb, tables_dev + (size_t)b0 * DL_TNS_NTAB * t.n11);
     }

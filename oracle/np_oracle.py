@@ -304,13 +304,14 @@ def tns_table_matrix(tab):
     return np.concatenate([np.array([tab[name] for name in TNS_NAMES]), tab['A'], tab['B']], axis=0)
 
 
-def tns_pktable(k, mu, wmu_ell, q, pk_q, f, qpar=1., qper=1., sigmav=0., fog='lorentzian', kernels=None, k11=None):
-    """``TNSPowerSpectrumMultipoles.calculate``, full_shape.py:865-899: dict name -> [n_ell, n_k] (A, B: [3, n_ell, n_k] for the b1^2, b1, 1 terms)."""
+def tns_pktable(k, mu, wmu_ell, q, pk_q, f, qpar=1., qper=1., sigmav=0., fog='lorentzian', kernels=None, k11=None, tab=None):
+    """``TNSPowerSpectrumMultipoles.calculate``, full_shape.py:865-899: dict name -> [n_ell, n_k] (A, B: [3, n_ell, n_k] for the b1^2, b1, 1 terms).
+    ``tab``: the 29 tables ``tns_table_matrix(tns_pt(...))`` on ``k11`` when the caller has them already (computed here otherwise)."""
     jac, kap, muap = ap_k_mu(k, mu, qpar=qpar, qper=qper)
     if fog == 'lorentzian': damping = 1. / (1. + (sigmav * kap * muap)**2 / 2.)**2.
     else: damping = np.exp(-(sigmav * kap * muap)**2)
     if k11 is None: k11 = tns_k11(k)
-    tab = tns_table_matrix(tns_pt(k11, q, weights_trapz(q), pk_q, kernels=kernels))
+    if tab is None: tab = tns_table_matrix(tns_pt(k11, q, weights_trapz(q), pk_q, kernels=kernels))
     t = jac * damping * np.moveaxis(interp1d(np.log10(kap), np.log10(k11), tab.T, method='cubic'), [0, 1], [1, 2])   # [29, n_k, n_mu]
     A, B = t[12:17], t[17:]
     m2 = muap**2

@@ -171,6 +171,36 @@ def section_stk():
             if marg: assert np.allclose(out[3][i], sol['x'], rtol=1e-7, atol=1e-9)
 
 
+def _odd_shapes(cases):
+    """The cases ``cases`` of tests/theory_shapes_cases.py (ragged table wavenumbers / template knots, n_kin on either side of the BAO workgroup sizes) against the oracle:
+    at 33 points and inside a 1100-row batch (one wavenumber per wave for the one-loop kernel unless forced otherwise), log-likelihood and theory vector, the last rows of
+    the batch among the compared ones."""
+    import theory_shapes_cases as tsc
+    for name in cases:
+        like, info = tsc.build(name)
+        ctx = like._get_context()
+        for size in (33, 1100):
+            theta = tsc.sample(like, size, seed=500 + size)
+            rows = tsc.spread_rows(size, count=6)
+            loglike, logprior, status, flat = ctx.eval_batch_host(theta, return_flattheory=True)
+            assert (status == 0).all(), (name, size)
+            ref_ll, ref_flat, _ = tsc.oracle_rows(like, info, theta[rows])
+            close(loglike[rows], ref_ll, '{} at {:d} rows vs oracle'.format(name, size))
+            err = np.abs(flat[rows] - ref_flat).max(axis=1) / np.abs(ref_flat).max(axis=1)
+            assert (err <= 1e-10).all(), (name, size, float(err.max()))
+        ctx.close()
+
+
+def section_tnsodd():
+    """the one-loop kernels at n11 = 11 / 61 knots and n11 = 14 / 14 knots: waves past the last table wavenumber, padded templates, a last round of pairs that is mostly padding"""
+    _odd_shapes(['tns_7_11_61_4', 'tns_9_14_14_16'])
+
+
+def section_baoodd():
+    """the BAO kernel at 9 and 258 wavenumbers, plain and with the phase-shift template: fewer wavenumbers than threads, a remainder past the largest workgroup"""
+    _odd_shapes(['bao_9', 'bao_258', 'bao_ps_9', 'bao_ps_258'])
+
+
 if __name__ == '__main__':
     for name in sys.argv[1:]:
         globals()['section_' + name]()

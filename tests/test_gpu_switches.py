@@ -12,9 +12,10 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 # (environment, sections of tests/switch_probe.py the switch can affect)
-SWITCHES = [({}, 'fs two ens emu bao tns png mh stk'),
-            ({'DL_TNS_WAVEK': '0'}, 'tns'), ({'DL_TNS_WAVEK': '1'}, 'tns'), ({'DL_TNS_W': '2'}, 'tns'), ({'DL_TNS_W': '4'}, 'tns'),                 # TNS loop kernel: split-K / one wavenumber per wave, whatever the batch
-            ({'DL_NO_TOEPLITZ': '1'}, 'fs two png'),                                        # general-knot spline solve (segmented Thomas) instead of the FIR form
+SWITCHES = [({}, 'fs two ens emu bao tns png mh stk tnsodd baoodd'),
+            ({'DL_TNS_WAVEK': '0'}, 'tns tnsodd'), ({'DL_TNS_WAVEK': '1'}, 'tns tnsodd'),                                              # TNS loop kernel: split-K / one wavenumber per wave, whatever the batch
+            ({'DL_TNS_W': '1'}, 'tnsodd'), ({'DL_TNS_W': '2'}, 'tns tnsodd'), ({'DL_TNS_W': '4'}, 'tns tnsodd'), ({'DL_TNS_W': '8'}, 'tnsodd'),   # ... every number of waves per wavenumber; tnsodd: table wavenumbers that leave waves without one (tests/theory_shapes_cases.py)
+            ({'DL_NO_TOEPLITZ': '1'}, 'fs two png tnsodd'),                                        # general-knot spline solve (segmented Thomas) instead of the FIR form
             ({'DL_XCD_LOCAL': '0'}, 'fs emu'), ({'DL_XCD_LOCAL': '2', 'DL_CHI2_GEMM_MAX': '512'}, 'fs'),
             ({'DL_CHI2_GEMM_MAX': '512'}, 'fs two'),                                     # 2537 rows through the LDS-DMA GEMM with the partial-chi2 epilogue
             ({'DL_CHI2_GEMM_MAX': '512', 'DL_NO_CHI2_BIG': '1'}, 'fs two'),              # ... through the split-K slabs + slab finalize
@@ -34,7 +35,7 @@ SWITCHES = [({}, 'fs two ens emu bao tns png mh stk'),
             ({'DL_NO_STK_SPLIT': '1'}, 'stk'),                                             # the stacked engine in one launch (dl_emulated_stacked_kernel: the round-5 form) instead of chains + feature GEMMs
             ({'DL_STK_OVERLAP': '1'}, 'stk'), ({'DL_STK_OVERLAP': '3'}, 'stk'), ({'DL_STK_OVERLAP': '4'}, 'stk'),   # dl_emulated_stacked_ov_kernel (round-6 experiment, measured slower, kept for the record): networks under the feature GEMM (3: no raised priority), split halves
             ({'DL_FM_NO_STAGE': '1'}, 'emu bao'),
-            ({'DL_BAO_THREADS': '64'}, 'bao'), ({'DL_BAO_THREADS': '128'}, 'bao'), ({'DL_BAO_THREADS': '256'}, 'bao'),
+            ({'DL_BAO_THREADS': '64'}, 'bao baoodd'), ({'DL_BAO_THREADS': '128'}, 'bao baoodd'), ({'DL_BAO_THREADS': '256'}, 'bao baoodd'),      # baoodd: 9 and 258 wavenumbers
             ({'DL_FFTLOG_GENERIC': '1'}, 'bao')]
 
 

@@ -145,7 +145,7 @@ int dl_cov_create(dl_cov** out, int device, int32_t n, int32_t n_theories, const
 }
 
 int dl_cov_apply(dl_cov* plan, const double* const* power_dev, int64_t B, double* cov_dev, void* hip_stream) {
-    if (!plan || !power_dev || !cov_dev || B < 0) return dl_fail("dl_cov_apply: invalid argument");
+    if (!plan || !power_dev || (B > 0 && !cov_dev) || B < 0) return dl_fail("dl_cov_apply: invalid argument");   // (an empty batch has no output buffer)
     if (B == 0) return 0;
     if (B > 65535) return dl_fail("dl_cov_apply: at most 65535 parameter points per call");
     hipStream_t stream = (hipStream_t)hip_stream;

@@ -582,7 +582,7 @@ int  dl_mlp_get_weights(dl_mlp* net, double* weights /* host, flat */, void* hip
  *   sym    [n_sym, 2]    pairs (row, col) of the diagonal blocks replaced by their mean with the transposed element (covariance.py:349-351);
  * theory t: n_ell[t] <= 5 multipoles on n_k[t] wavenumbers, ell0[t] = position of the monopole (-1: none), shotnoise[t] added to it.
  * dl_cov_apply: power_dev[t] = device array [B, n_ell[t], n_k[t]] (e.g. from dl_eval_theory), cov_dev [B, n, n] device output (zero where no cell writes); asynchronous
- * on ``hip_stream``; B <= 65535. */
+ * on ``hip_stream``; B <= 65535 (B = 0: nothing to do, cov_dev may be null). */
 typedef struct dl_cov dl_cov;
 int  dl_cov_create(dl_cov** out, int device, int32_t n, int32_t n_theories, const int32_t* n_ell, const int32_t* n_k, const int32_t* ell0, const double* shotnoise,
                    int64_t n_cells, const int32_t* cell_i, const double* cell_d, int64_t n_points, const int32_t* pt_i, const double* pt_d, int32_t n_gtab, const double* gtab,

@@ -936,12 +936,17 @@ def mlp_loss_and_grad(layers, x, y, activation='silu'):
     return loss, grads
 
 
-def mlp_adam(layers, x, y, batch, nsteps, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, activation='silu'):
-    """``nsteps`` Adam steps on consecutive chunks of ``batch`` samples (step t uses chunk t mod (S // batch)); returns (layers, losses)."""
+def mlp_adam(layers, x, y, batch, nsteps, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, activation='silu', state=None):
+    """``nsteps`` Adam steps on consecutive chunks of ``batch`` samples (step t uses chunk t mod (S // batch)); returns (layers, losses).
+    To continue a run (stages with their own ``lr``, as ``emulators.fit_mlp`` trains): ``state`` = ``{}`` for the first stage, then the state returned by the stage
+    before (Adam moments and the step count, which also rotates the chunks: both carry over, like in ``dl_mlp_train``); returns (layers, losses, state)."""
     layers = [(kernel.copy(), bias.copy()) for kernel, bias in layers]
-    moments = [[np.zeros_like(kernel), np.zeros_like(bias), np.zeros_like(kernel), np.zeros_like(bias)] for kernel, bias in layers]
+    if state:
+        moments, step = [[m.copy() for m in moment] for moment in state['moments']], int(state['step'])
+    else:
+        moments, step = [[np.zeros_like(kernel), np.zeros_like(bias), np.zeros_like(kernel), np.zeros_like(bias)] for kernel, bias in layers], 0
     chunks, losses = len(x) // batch, []
-    for t in range(1, nsteps + 1):
+    for t in range(step + 1, step + nsteps + 1):
         c = (t - 1) % chunks
         loss, grads = mlp_loss_and_grad(layers, x[c * batch:(c + 1) * batch], y[c * batch:(c + 1) * batch], activation)
         losses.append(loss)
@@ -951,6 +956,7 @@ def mlp_adam(layers, x, y, batch, nsteps, lr=1e-3, beta1=0.9, beta2=0.999, eps=1
                 m = moments[il][ip] = beta1 * moments[il][ip] + (1. - beta1) * g
                 v = moments[il][2 + ip] = beta2 * moments[il][2 + ip] + (1. - beta2) * g * g
                 layers[il][ip][...] -= lr * (m / c1) / (np.sqrt(v / c2) + eps)
+    if state is not None: return layers, np.array(losses), dict(moments=moments, step=step + nsteps)
     return layers, np.array(losses)
 
 

@@ -1,7 +1,10 @@
 """Gaussian covariance matrices computed by the REFERENCE (desilike/observables/galaxy_clustering/covariance.py:274-456, ``ObservablesCovarianceMatrix``) for
 power-spectrum and correlation-function multipoles, with the theory spectra it consumed.  Build container only:
 
-    python tests/golden/make_covariance_fixture.py
+    python tests/golden/make_covariance_fixture.py          # covariance.npz: block kinds a, b, c
+    python tests/golden/make_covariance_fixture.py extra    # covariance_extra.npz: d (xi listed before P: the cross block that is not transposed), e (two P observables
+                                                            # of different binning: partly overlapping, nested and disjoint bins), f (xi alone, ells (0, 2, 4)),
+                                                            # g (P with ells (2, 4): the reference's theory then has no monopole, so no shot noise enters)
 
 The reference's ``utils.weights_trapz`` relies on ``jnp.insert`` clamping an out-of-range index (jax is absent here and numpy raises): replaced by the same weights
 written for numpy -- the one reference line replaced, as in make_golden.cfg2_fc_syst."""
@@ -81,5 +84,33 @@ def main():
     print('saved', fn, '{:.1f} kB'.format(os.path.getsize(fn) / 1e3), {k: np.shape(v) for k, v in out.items() if 'covariance' in k or 'power' in k or '_k' in k})
 
 
+def main_extra():
+    out = {}
+    points = [dict(b1=2., qpar=1., df=1.), dict(b1=1.5, qpar=1.02, df=0.9)]
+
+    def pk_observable(kedges, ells, **kwargs):
+        return TracerPowerSpectrumMultipolesObservable(data={'b1': 2.}, kedges=kedges, ells=ells, theory=KaiserTracerPowerSpectrumMultipoles(template=ShapeFitPowerSpectrumTemplate(z=0.5)),
+                                                       shotnoise=1e4, **kwargs)
+
+    def xi_observable(sedges, ells, **kwargs):
+        return TracerCorrelationFunctionMultipolesObservable(data={'b1': 2.}, sedges=sedges, ells=ells,
+                                                             theory=KaiserTracerCorrelationFunctionMultipoles(template=ShapeFitPowerSpectrumTemplate(z=0.5)), **kwargs)
+
+    # (d) xi_ell listed before P_ell: the (xi, P) block as computed, the (P, xi) block its transpose
+    capture('d', ObservablesCovarianceMatrix([xi_observable(np.linspace(20., 140., 7), (0, 2)), pk_observable(np.linspace(0.01, 0.15, 8), (0, 2))],
+                                             footprints=BoxFootprint(volume=1e10, nbar=1e-4), resolution=2), points[:1], out)
+    # (e) two P_ell observables, bins of width 0.02 from 0.01 and of width 0.03 from 0.025: partial intersections, bins of one inside bins of the other, empty ones
+    capture('e', ObservablesCovarianceMatrix([pk_observable(np.linspace(0.01, 0.19, 10), (0, 2)), pk_observable(np.linspace(0.025, 0.205, 7), (0, 2, 4))],
+                                             footprints=[BoxFootprint(volume=1e10, nbar=1e-4), BoxFootprint(volume=8e9, nbar=2e-4)], resolution=3), points, out)
+    # (f) xi_ell alone, ells (0, 2, 4)
+    capture('f', ObservablesCovarianceMatrix(xi_observable(np.linspace(20., 160., 8), (0, 2, 4)), footprints=BoxFootprint(volume=1e10, nbar=1e-4), resolution=2), points[:1], out)
+    # (g) P_ell, ells (2, 4): the theory takes the observable's multipoles and has no monopole
+    capture('g', ObservablesCovarianceMatrix(pk_observable(np.linspace(0.02, 0.2, 10), (2, 4)), footprints=BoxFootprint(volume=1e10, nbar=1e-4), resolution=2), points, out)
+    assert list(out['g_theory0_ells']) == [2, 4]
+    fn = os.path.join(here, 'covariance_extra.npz')
+    np.savez_compressed(fn, **out)
+    print('saved', fn, '{:.1f} kB'.format(os.path.getsize(fn) / 1e3), {k: np.shape(v) for k, v in out.items() if 'covariance' in k or 'power' in k or '_k' in k or 'ells' in k})
+
+
 if __name__ == '__main__':
-    main()
+    main_extra() if sys.argv[1:] == ['extra'] else main()

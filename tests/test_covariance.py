@@ -1,5 +1,7 @@
 """Gaussian covariance of power-spectrum / correlation-function multipoles (reference: observables/galaxy_clustering/covariance.py:274-456)
-against the reference's own matrices (tests/golden/covariance.npz <- tests/golden/make_covariance_fixture.py): the oracle on CPU, the device kernel on the GPU."""
+against the reference's own matrices (tests/golden/covariance.npz, covariance_extra.npz <- tests/golden/make_covariance_fixture.py): the oracle on CPU, the device kernel
+on the GPU.  Tags a, b, c: P, P with different k-ranges, P and xi; d: xi listed before P; e: two P observables of different binning; f: xi alone, ells (0, 2, 4);
+g: P with ells (2, 4), a theory without monopole."""
 import os
 
 import numpy as np
@@ -8,8 +10,11 @@ import pytest
 from oracle import np_oracle as orc
 
 
+TAGS = ['a', 'b', 'c', 'd', 'e', 'f', 'g']
+
+
 def load(tag):
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'covariance.npz'))
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'covariance.npz' if tag in 'abc' else 'covariance_extra.npz'))
     observables, theories = [], []
     io = 0
     while '{}_obs{:d}_kind'.format(tag, io) in g.files:
@@ -22,7 +27,7 @@ def load(tag):
     return g, observables, theories, int(g[tag + '_resolution'])
 
 
-@pytest.mark.parametrize('tag', ['a', 'b', 'c'])
+@pytest.mark.parametrize('tag', TAGS)
 def test_oracle_covariance_vs_reference(tag):
     g, observables, theories, resolution = load(tag)
     ref = g[tag + '_covariance']
@@ -33,7 +38,7 @@ def test_oracle_covariance_vs_reference(tag):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('tag', ['a', 'b', 'c'])
+@pytest.mark.parametrize('tag', TAGS)
 def test_gpu_covariance_plan_vs_reference(tag):
     """dl_cov_* through ctypes on the theory spectra the reference consumed: every block kind (P x P, xi x P, xi x xi), every parameter point of the fixture."""
     import torch
@@ -42,7 +47,7 @@ def test_gpu_covariance_plan_vs_reference(tag):
     g, observables, theories, resolution = load(tag)
     desc = [dict(obs, theory_k=theory['k'], theory_ells=theory['ells']) for obs, theory in zip(observables, theories)]
     arrays = CovariancePlanBuilder(desc, resolution=resolution).arrays()
-    plan = CovariancePlan(arrays['n'], [len(t['ells']) for t in theories], [len(t['k']) for t in theories], [list(t['ells']).index(0) for t in theories], [obs['shotnoise'] for obs in observables],
+    plan = CovariancePlan(arrays['n'], [len(t['ells']) for t in theories], [len(t['k']) for t in theories], [list(t['ells']).index(0) if 0 in t['ells'] else -1 for t in theories], [obs['shotnoise'] for obs in observables],
                           arrays['cell_i'], arrays['cell_d'], arrays['pt_i'], arrays['pt_d'], arrays['gtab'], arrays['sym'], device=0)
     powers = [torch.as_tensor(theory['power'], dtype=torch.float64, device='cuda').contiguous() for theory in theories]
     got = plan.apply(powers).cpu().numpy()

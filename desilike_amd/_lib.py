@@ -33,6 +33,8 @@ SYMBOLS = {
     'dl_eval_logposterior_grad': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_fisher': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_data_set': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int32]),
+    'dl_data_set_solved': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int32]),
+    'dl_eval_solved_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_logposterior_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_fisher_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_fisher_analytic': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -580,12 +582,14 @@ class Context(_Handle):
         return hessian, gradient, offset
 
     # ---- data batch (dl_data_set; csrc/dl_data_batch.h): many data vectors against one context ----
-    def set_data_batch(self, flatdata):
+    def set_data_batch(self, flatdata, solved=False):
         """Give the context ``flatdata [M, n_data]`` (host array, rows in the order of the context's own data vector) as its data batch (``dl_data_set``); ``None`` or
-        an empty array frees it.  Shape and finiteness are checked here, before any device call."""
+        an empty array frees it.  Shape and finiteness are checked here, before any device call.  ``solved=True``: ``dl_data_set_solved``, which contexts with
+        analytically solved parameters accept too -- their data-batch calls solve these parameters per point and per data vector (csrc/dl_data_batch_marg.h)."""
         if flatdata is None: flatdata = np.empty((0, self.n_data), dtype='f8')
         flatdata = check_data_batch(flatdata, self.n_data)
-        self._check(self._lib.dl_data_set(self._handle, _f64_ptr(flatdata), flatdata.shape[0]))
+        setter = self._lib.dl_data_set_solved if solved else self._lib.dl_data_set
+        self._check(setter(self._handle, _f64_ptr(flatdata), flatdata.shape[0]))
         return flatdata.shape[0]
 
     @property
@@ -623,6 +627,37 @@ class Context(_Handle):
         out = self.eval_logposterior_data(th, index=index, status=status)
         torch.cuda.synchronize(device)
         return out.cpu().numpy(), status.cpu().numpy()
+
+    def eval_solved_data(self, theta, index, out=None, status=None, solved=None, stream=None):
+        """The paired call of :meth:`eval_logposterior_data` on a context with solved parameters, plus their values (``dl_eval_solved_data``): ``theta [B, P]`` float64
+        device tensor, ``index [B]`` int32 device tensor -> ``(out [B], solved [B, n_solved])``, point b given data vector ``index[b]``.  Asynchronous."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(theta.device).cuda_stream
+        B = theta.shape[0]
+        theta = self._device_theta(theta, stream)
+        assert index.is_contiguous() and index.dtype == torch.int32 and tuple(index.shape) == (B,)
+        if out is None: out = torch.empty((B,), dtype=torch.float64, device=theta.device)
+        if solved is None: solved = torch.empty((B, self.n_solved), dtype=torch.float64, device=theta.device)
+        assert out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == (B,)
+        assert solved.is_contiguous() and solved.dtype == torch.float64 and tuple(solved.shape) == (B, self.n_solved)
+        assert status is None or (status.is_contiguous() and status.dtype == torch.int32 and tuple(status.shape) == (B,))
+        self._check(self._lib.dl_eval_solved_data(self._handle, ctypes.c_void_p(theta.data_ptr()), B, ctypes.c_void_p(index.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                                  None if status is None else ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(solved.data_ptr()), ctypes.c_void_p(stream)))
+        return out, solved
+
+    def eval_solved_data_host(self, theta, index):
+        """numpy in / numpy out: (logposterior [B], status [B], solved [B, n_solved]); stages through device tensors."""
+        import torch
+        theta = np.ascontiguousarray(np.atleast_2d(theta), dtype='f8')
+        index = np.ascontiguousarray(index, dtype='i4')
+        if index.shape != (theta.shape[0],): raise ValueError('index must have shape ({:d},), found {}'.format(theta.shape[0], index.shape))
+        device = torch.device('cuda', self.device)
+        th = torch.as_tensor(theta, dtype=torch.float64, device=device).contiguous()
+        status = torch.zeros(theta.shape[0], dtype=torch.int32, device=device)
+        out, solved = self.eval_solved_data(th, torch.as_tensor(index, device=device), status=status)
+        torch.cuda.synchronize(device)
+        return out.cpu().numpy(), status.cpu().numpy(), solved.cpu().numpy()
 
     def eval_fisher_data(self, centers, steps, index, hessian=None, gradient=None, offset=None, stream=None):
         """:meth:`eval_fisher` with the residual of centre b taken against data vector ``index[b]`` of the data batch (``dl_eval_fisher_data``; ``index`` int32 device

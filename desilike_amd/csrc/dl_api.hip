@@ -17,6 +17,7 @@
 #include "dl_prior.h"
 #include "dl_sample_solved.h"
 #include "dl_data_batch.h"
+#include "dl_data_batch_marg.h"
 
 static thread_local std::string g_last_error;
 void dl_set_last_error(const char* msg) { g_last_error = msg ? msg : ""; }
@@ -133,6 +134,9 @@ struct dl_ctx {
     int n_data_batch = 0;
     double* data_bias_dev = nullptr;
     int32_t* data_index_ws = nullptr;   // [DL_CHUNK] checked data indices of the centres of a pass of dl_eval_fisher_data
+    // ... of a context with solved parameters (dl_data_set_solved, dl_data_batch_marg.h): rows [cap, 1 + n_var, N_pad] and records [cap, DL_DBM_REC] of the points of a pass
+    double *dbm_rows = nullptr, *dbm_rec = nullptr;
+    int64_t dbm_cap = 0;
     // the workspaces are shared by every call on this context: a call on another stream than the previous one waits for it (event recorded on the old stream
     // at the moment of the switch: calls that stay on one stream pay nothing)
     hipStream_t last_stream = nullptr;
@@ -559,6 +563,7 @@ void dl_destroy(dl_ctx* ctx) {
     if (ctx->ss_status) (void)hipFree(ctx->ss_status);
     if (ctx->data_bias_dev) (void)hipFree(ctx->data_bias_dev);
     if (ctx->data_index_ws) (void)hipFree(ctx->data_index_ws);
+    for (double* p : {ctx->dbm_rows, ctx->dbm_rec}) if (p) (void)hipFree(p);
     void* ptrs[] = {ctx->arena_dev, ctx->priors_dev, ctx->wt_white_dev, ctx->wt_frag_dev, ctx->bias_white_dev, ctx->wt_full_dev, ctx->bias_full_dev, ctx->wh_dev,
                     ctx->bias_wh_dev, ctx->flatdata_dev, ctx->transform_dev, ctx->tconst_dev, ctx->power_ws, ctx->delta_ws, ctx->flat_ws, ctx->stencil_ws, ctx->theta_stage, ctx->out_stage,
                     ctx->status_stage, ctx->gemm_counters, ctx->obs_array_dev, ctx->ws_scratch, ctx->prior_rec_ws};
@@ -652,7 +657,26 @@ static int dl_reserve(dl_ctx* ctx, int64_t B) {
 struct DlDataEval {
     const int32_t* index;   // [B] device, or null: every data vector (out [B, M])
     double* out;
+    double* solved;         // [B, n_solved] device, or null (dl_eval_solved_data: paired calls on a context with solved parameters)
 };
+
+// workspaces of the data-batch finalize of a context with solved parameters: grown like those of dl_reserve, never on the hot path after the first call of a shape
+static int dl_dbm_reserve(dl_ctx* ctx, int64_t B) {
+    int64_t need = std::min<int64_t>(B, DL_CHUNK);
+    if (need <= ctx->dbm_cap) return 0;
+    need = std::min<int64_t>(std::max<int64_t>(need, 1024), DL_CHUNK);
+    if (ctx->dbm_cap > 0) DL_HIP_CHECK(ctx, hipDeviceSynchronize());   // (kernels of earlier calls may still use the buffers about to be freed)
+    for (double** p : {&ctx->dbm_rows, &ctx->dbm_rec}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    ctx->dbm_cap = 0;
+    const size_t rows = (size_t)need * (1 + ctx->n_var) * ctx->N_pad;
+    DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->dbm_rows, rows * sizeof(double)));
+    DL_HIP_CHECK(ctx, hipMalloc((void**)&ctx->dbm_rec, (size_t)need * DL_DBM_REC * sizeof(double)));
+    DL_HIP_CHECK(ctx, hipMemset(ctx->dbm_rows, 0, rows * sizeof(double)));
+    DL_HIP_CHECK(ctx, hipMemset(ctx->dbm_rec, 0, (size_t)need * DL_DBM_REC * sizeof(double)));
+    DL_HIP_CHECK(ctx, hipDeviceSynchronize());   // (the memsets run on the null stream: see dl_reserve)
+    ctx->dbm_cap = need;
+    return 0;
+}
 
 static int dl_eval_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, double* loglike_dev, double* logprior_dev, double* flattheory_dev, int32_t* status_dev,
                         double* solved_dev, void* hip_stream, int post_mode, double* hessian_dev = nullptr, const DlDataEval* data = nullptr) {
@@ -794,7 +818,12 @@ static int dl_eval_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, double*
                                         stream, ctx->n_white);
         }
         prof_phase(2);
-        if (data)
+        if (data && ctx->n_solved > 0)   // per-point records, then the solve of every pair (dl_data_batch_marg.h)
+            dl_launch_data_marg(ctx->delta_ws, ctx->N_pad, ctx->n_white, R, n_slabs, slab_stride, ctx->marg, ctx->data_bias_dev, ctx->N_pad, ctx->n_data_batch,
+                                data->index ? data->index + b0 : nullptr, th, P, ctx->priors_dev, nb, ctx->dbm_rows, ctx->dbm_rec,
+                                data->out + (size_t)b0 * (data->index ? 1 : ctx->n_data_batch), status_dev ? status_dev + b0 : nullptr,
+                                data->solved ? data->solved + (size_t)b0 * ctx->n_solved : nullptr, stream);
+        else if (data)
             dl_launch_data_finalize(ctx->delta_ws, ctx->N_pad, ctx->n_white, n_slabs, slab_stride, ctx->data_bias_dev, ctx->N_pad, ctx->n_data_batch,
                                     data->index ? data->index + b0 : nullptr, th, P, ctx->priors_dev, nb, data->out + (size_t)b0 * (data->index ? 1 : ctx->n_data_batch),
                                     status_dev ? status_dev + b0 : nullptr, stream);
@@ -952,19 +981,20 @@ int dl_eval_fisher_data(dl_ctx* ctx, const double* centers_dev, const double* st
     if (!ctx) { g_last_error = "dl_eval_fisher_data: null context"; return 1; }
     if (ctx->n_data_batch == 0) return dl_fail(ctx, "dl_eval_fisher_data: the context has no data batch (dl_data_set)");
     if (B > 0 && !data_index_dev) return dl_fail(ctx, "dl_eval_fisher_data: null data index");
+    if (ctx->n_solved > 0) return dl_fail(ctx, "dl_eval_fisher_data: the context has analytically solved parameters (vary them)");
     return dl_eval_fisher_impl(ctx, centers_dev, steps_dev, B, data_index_dev, hessian_dev, gradient_dev, offset_dev, hip_stream);
 }
 
 // Data batch: M data vectors next to the context's own (dl_data_batch.h).  Host arithmetic of dl_create (DlWhitenHost::apply), one row of [M, N_pad] per vector.
-int dl_data_set(dl_ctx* ctx, const double* flatdata, int32_t M) {
-    if (!ctx) { g_last_error = "dl_data_set: null context"; return 1; }
-    if (M < 0 || M > DL_DB_MAX_M) return dl_fail(ctx, "dl_data_set: the number of data vectors must lie in [0, 65536]");
-    if (M > 0 && !flatdata) return dl_fail(ctx, "dl_data_set: null data");
-    if (ctx->any_transform) return dl_fail(ctx, "dl_data_set: the context has an observable transform: its residual is not additive in the data");
-    if (ctx->n_solved > 0) return dl_fail(ctx, "dl_data_set: the context has analytically solved parameters: create it with these parameters varied, or with the marginalised precision");
+static int dl_data_set_impl(dl_ctx* ctx, const double* flatdata, int32_t M, bool solved_ok, const std::string& fn) {
+    if (!ctx) { g_last_error = fn + ": null context"; return 1; }
+    if (M < 0 || M > DL_DB_MAX_M) return dl_fail(ctx, fn + ": the number of data vectors must lie in [0, 65536]");
+    if (M > 0 && !flatdata) return dl_fail(ctx, fn + ": null data");
+    if (ctx->any_transform) return dl_fail(ctx, fn + ": the context has an observable transform: its residual is not additive in the data");
+    if (ctx->n_solved > 0 && !solved_ok) return dl_fail(ctx, fn + ": the context has analytically solved parameters: create it with these parameters varied, or with the marginalised precision");
     const int n = ctx->n_data;
     for (int64_t e = 0; e < (int64_t)M * n; ++e)
-        if (!std::isfinite(flatdata[e])) return dl_fail(ctx, "dl_data_set: data vector " + std::to_string(e / n) + " has a NaN or infinite entry");
+        if (!std::isfinite(flatdata[e])) return dl_fail(ctx, fn + ": data vector " + std::to_string(e / n) + " has a NaN or infinite entry");
     DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     DL_HIP_CHECK(ctx, hipDeviceSynchronize());   // kernels of earlier calls (any stream) may still read the table about to be replaced
     if (ctx->data_bias_dev) { (void)hipFree(ctx->data_bias_dev); ctx->data_bias_dev = nullptr; }
@@ -982,11 +1012,33 @@ int dl_data_set(dl_ctx* ctx, const double* flatdata, int32_t M) {
     return 0;
 }
 
+int dl_data_set(dl_ctx* ctx, const double* flatdata, int32_t M) { return dl_data_set_impl(ctx, flatdata, M, false, "dl_data_set"); }
+
+// ... for contexts with analytically solved parameters too: their data-batch calls solve them per point and per data vector (dl_data_batch_marg.h)
+int dl_data_set_solved(dl_ctx* ctx, const double* flatdata, int32_t M) { return dl_data_set_impl(ctx, flatdata, M, true, "dl_data_set_solved"); }
+
 int dl_eval_logposterior_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, double* out_dev, int32_t* status_dev, void* hip_stream) {
     if (!ctx) { g_last_error = "dl_eval_logposterior_data: null context"; return 1; }
     if (ctx->n_data_batch == 0) return dl_fail(ctx, "dl_eval_logposterior_data: the context has no data batch (dl_data_set)");
     if (B > 0 && !out_dev) return dl_fail(ctx, "dl_eval_logposterior_data: null output");
-    const DlDataEval data = {data_index_dev, out_dev};
+    if (ctx->n_solved > 0) {
+        DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+        if (dl_dbm_reserve(ctx, B)) return 1;
+    }
+    const DlDataEval data = {data_index_dev, out_dev, nullptr};
+    return dl_eval_impl(ctx, theta_dev, B, nullptr, nullptr, nullptr, status_dev, nullptr, hip_stream, 1, nullptr, &data);
+}
+
+// the paired call on a context with solved parameters, plus the solved values x0 + dx of point b given its data vector
+int dl_eval_solved_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, double* out_dev, int32_t* status_dev, double* solved_dev,
+                        void* hip_stream) {
+    if (!ctx) { g_last_error = "dl_eval_solved_data: null context"; return 1; }
+    if (ctx->n_data_batch == 0) return dl_fail(ctx, "dl_eval_solved_data: the context has no data batch (dl_data_set_solved)");
+    if (ctx->n_solved == 0) return dl_fail(ctx, "dl_eval_solved_data: no analytically solved parameter in this likelihood");
+    if (B > 0 && (!out_dev || !solved_dev || !data_index_dev)) return dl_fail(ctx, "dl_eval_solved_data: null data index or output");
+    DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (dl_dbm_reserve(ctx, B)) return 1;
+    const DlDataEval data = {data_index_dev, out_dev, solved_dev};
     return dl_eval_impl(ctx, theta_dev, B, nullptr, nullptr, nullptr, status_dev, nullptr, hip_stream, 1, nullptr, &data);
 }
 

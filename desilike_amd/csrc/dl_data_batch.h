@@ -61,7 +61,7 @@ DL_HD double dl_db_pair_chi2(const double* y, const double* bias, int n) {
     return dl_db_tree(p);
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(DL_DB_NO_KERNELS)   // (DL_DB_NO_KERNELS: the functions above alone, for dl_data_batch_marg.h in dl_kernels.hip)
 #include "dl_kernels.h"
 #include "dl_prior.h"
 

@@ -2123,3 +2123,9 @@ void dl_launch_emu_jac_rows(const DlObsDev& obs, const double* U, int64_t ldu, c
     const size_t shm = (size_t)(1 + n_params) * DL_FG_MONO_LD * sizeof(double);
     DL_LAUNCH(dl_emu_jac_rows_kernel, dim3((unsigned)B), dim3(128), shm, stream, cols, U, ldu, cmono, dmono, bias, n_params, n_live, N_pad, resid, ldr, rows, ld, B);
 }
+
+// ---- data batch of a context with analytically solved parameters: per-point records, per-pair solves (dl_data_batch_marg.h) ----
+#include <type_traits>
+#define DL_DB_NO_KERNELS   // (dl_data_batch.h: its reduction functions alone; its kernels live in dl_api.hip)
+#define DL_DBM_KERNELS
+#include "dl_data_batch_marg.h"

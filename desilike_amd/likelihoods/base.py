@@ -167,15 +167,32 @@ class DataBatch(object):
     The context behind it is a private one (the likelihood's own contexts are shared with its samplers), compiled from the configuration samplers consume
     (:meth:`ObservablesGaussianLikelihood._get_posterior_context`): the plain context without analytically solved parameters; the marginalised-precision context when
     every solved parameter has a constant derivative row -- the data shift ``(x0 - loc) T`` of that construction is added to every data vector and its offset to every
-    value.  Point-dependent solved rows (velocileptors counter terms) are out of scope: ``NotImplementedError``."""
+    value.  Point-dependent solved rows (velocileptors counter terms) are out of that construction's scope: ``NotImplementedError``.
 
-    def __init__(self, likelihood, data):
+    ``solve='point'``: the private context is compiled from the likelihood's own per-point configuration (:meth:`ObservablesGaussianLikelihood._get_context`: the
+    solved parameters with their ``marg`` keys, no data shift, no offset) and the solved parameters are solved for every point AND every data vector
+    (``dl_data_set_solved``; csrc/dl_data_batch_marg.h) -- any solved likelihood, constant rows included; :meth:`solved` then returns their values."""
+
+    def __init__(self, likelihood, data, solve='constant'):
         from .._lib import Context, check_data_batch
+        if solve not in ('constant', 'point'):
+            raise ValueError("solve must be 'constant' or 'point', found {!r}".format(solve))
         likelihood.initialize()
-        self.likelihood = likelihood
+        self.likelihood, self.solve = likelihood, solve
         sizes = [obs.wmatrix.size for obs in likelihood.observables]
         flatdata = check_data_batch(flatten_data_batch(data, sizes), sum(sizes))     # (shape and finiteness: before any device call)
         solved = likelihood.solved_params
+        if solve == 'point':
+            if not len(solved):
+                raise ValueError("solve='point' needs a likelihood with analytically solved parameters")
+            likelihood._get_context()
+            spec = likelihood._context_specs[()]
+            self.shift = np.concatenate([np.ravel(ospec['flatdata']) for ospec in spec['observables']]) - np.concatenate(likelihood._flatdata_list())   # ('.prec' parameters)
+            self.offset = 0.
+            self.flatdata = flatdata
+            self.context = Context(spec, device=likelihood.device)
+            self.context.set_data_batch(flatdata + self.shift, solved=True)
+            return
         if len(solved) and not likelihood._solved_are_constant():
             raise NotImplementedError('data batch with analytically solved parameters whose derivative rows depend on the point ({}): use GaussNewtonProfiler.maximize_batch, '
                                       'which varies them with the other parameters'.format(solved.names()))
@@ -196,6 +213,11 @@ class DataBatch(object):
     def logposterior(self, values, index=None):
         """``values [B, n_varied]`` (columns ordered as ``likelihood.varied_params``) -> log-posterior ``[B, M]`` of every point given every data vector; with
         ``index [B]`` (integers in ``[0, M)``) -> ``[B]``, point b given data vector ``index[b]``.  Samplers' conventions: -inf outside the prior."""
+        values, index = self._check_values(values, index)
+        out, _ = self.context.eval_logposterior_data_host(values, index=index)
+        return out + self.offset
+
+    def _check_values(self, values, index):
         values = np.ascontiguousarray(np.atleast_2d(values), dtype='f8')
         nvaried = len(self.likelihood.varied_params)
         if values.shape[1] != nvaried:
@@ -206,8 +228,17 @@ class DataBatch(object):
                 raise ValueError('index must be {:d} integers, found shape {} and type {}'.format(values.shape[0], index.shape, index.dtype))
             if index.size and (index.min() < 0 or index.max() >= self.size):
                 raise ValueError('index must lie in [0, {:d})'.format(self.size))
-        out, _ = self.context.eval_logposterior_data_host(values, index=index)
-        return out + self.offset
+        return values, index
+
+    def solved(self, values, index):
+        """``values [B, n_varied]``, ``index [B]`` (integers in ``[0, M)``) -> ``[B, n_solved]``: the analytically solved parameters of point b given data vector
+        ``index[b]``, columns ordered as ``likelihood.solved_params`` (``dl_eval_solved_data``).  Batches made with ``solve='point'`` only."""
+        if self.solve != 'point':
+            raise ValueError("the solved parameters of a data batch are available with data_batch(data, solve='point')")
+        if index is None:
+            raise ValueError('index must be {:d} integers, found None'.format(np.atleast_2d(values).shape[0]))
+        values, index = self._check_values(values, index)
+        return self.context.eval_solved_data_host(values, index)[2]
 
 
 class ObservablesGaussianLikelihood(BaseGaussianLikelihood):
@@ -786,9 +817,11 @@ class ObservablesGaussianLikelihood(BaseGaussianLikelihood):
                     logposterior += offset
         return logposterior
 
-    def data_batch(self, data):
-        """This likelihood against many data vectors: :class:`DataBatch` (``data``: array ``[M, n_data]`` in ``flatdata`` order, or a list of per-observable arrays)."""
-        return DataBatch(self, data)
+    def data_batch(self, data, solve='constant'):
+        """This likelihood against many data vectors: :class:`DataBatch` (``data``: array ``[M, n_data]`` in ``flatdata`` order, or a list of per-observable arrays).
+        ``solve``: 'constant' (analytically solved parameters folded into the precision: constant derivative rows only) or 'point' (solved per point and per data
+        vector: any solved likelihood)."""
+        return DataBatch(self, data, solve=solve)
 
     @property
     def size(self):
@@ -855,10 +888,12 @@ class SumLikelihood(BaseLikelihood):
         self.initialize()
         return self._fused.evaluate_logposterior(*args, **kwargs)
 
-    def data_batch(self, data):
+    def data_batch(self, data, solve='constant'):
         """:meth:`ObservablesGaussianLikelihood.data_batch` of the fused likelihood: the observables of the members one after the other."""
+        if solve not in ('constant', 'point'):
+            raise ValueError("solve must be 'constant' or 'point', found {!r}".format(solve))
         self.initialize()
-        return self._fused.data_batch(data)
+        return self._fused.data_batch(data, solve=solve)
 
     @property
     def size(self):

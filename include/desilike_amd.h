@@ -223,6 +223,22 @@ int  dl_data_set(dl_ctx* ctx, const double* flatdata, int32_t M);
  * kernels or the emulated feature path, split-K window GEMM or feature GEMM, then the finalize of csrc/dl_data_batch.h: direct differences, a fixed accumulation
  * order).  Works in passes over B like dl_eval_batch.  Returns 1 without a data batch.  Asynchronous on ``hip_stream``. */
 int  dl_eval_logposterior_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, double* out_dev, int32_t* status_dev, void* hip_stream);
+/* Data batch of a context WITH analytically solved parameters ('.marg' / '.best': csrc/dl_data_batch_marg.h): the solved parameters are solved per point AND per
+ * data vector -- the derivative rows, their Gram matrix H, the factor of H + diag(prec) and the log-determinant belong to the point and are formed once per point;
+ * the residual d = y + bias_m, G00 = |d|^2 (direct differences, the order of csrc/dl_data_batch.h), gd = Tt d, the two substitutions and the assembly of the value
+ * belong to the pair.  dl_data_set_solved: the contract of dl_data_set (whitening, replacement, M = 0, M <= 65536, NaN / infinite values refused, a refused call
+ * leaves the batch as it was, "n_data_batch"), accepted by contexts with solved parameters as well (n_s = 1 .. 16, any '.marg' / '.best' mask, constant and
+ * point-dependent rows, window-GEMM slabs and the emulated feature routes); observable transforms are still refused; on a context without solved parameters it is
+ * dl_data_set.  dl_data_set itself keeps refusing solved contexts.  On such a context dl_eval_logposterior_data has the same outputs and conventions: cross
+ * [B, M], paired [B], the same bits in both, values that do not depend on M, on the tile or (at an equal number of split-K slabs) on B; status_dev [B] describes the
+ * point: NaN input, out of prior, DL_STATUS_NONFINITE for a pivot that is not positive (every data vector then gives -inf) or a non-finite value against data
+ * vector 0.  dl_eval_fisher_data refuses such a context. */
+int  dl_data_set_solved(dl_ctx* ctx, const double* flatdata, int32_t M);
+/* The paired call on a context with solved parameters plus the solved values: solved_dev [B, n_solved] = x0 + dx of point b given data vector data_index_dev[b]
+ * (the nuisance best fits of a "fit every mock" run; NaN for an index outside [0, M)).  out_dev [B] and status_dev as dl_eval_logposterior_data, the same bits.
+ * Returns 1 without a data batch or on a context without solved parameters. */
+int  dl_eval_solved_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, double* out_dev, int32_t* status_dev, double* solved_dev,
+                         void* hip_stream);
 /* dl_eval_fisher with the residual of centre b taken against data vector data_index_dev[b] of the data batch: same stencil, outputs, conventions (no 1/2) and limits
  * (P <= 31, no solved parameter).  The Hessian does not depend on the data.  An index outside [0, M): NaN offset and gradient for that centre. */
 int  dl_eval_fisher_data(dl_ctx* ctx, const double* centers_dev, const double* steps_dev, int64_t B, const int32_t* data_index_dev, double* hessian_dev, double* gradient_dev,

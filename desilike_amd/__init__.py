@@ -11,5 +11,6 @@ from ._lib import Context, LibraryError  # noqa: F401
 from .base import BaseCalculator, PipelineError, vmap  # noqa: F401
 from .parameter import Parameter, ParameterPrior, ParameterCollection, Samples  # noqa: F401
 from .solved import sample_solved  # noqa: F401
+from .mock_sampler import MockEmceeSampler  # noqa: F401
 
 __version__ = '0.1.0'

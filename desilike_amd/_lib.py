@@ -61,6 +61,13 @@ SYMBOLS = {
     'dl_ensemble_get_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
     'dl_ensemble_set_counter': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
     'dl_ensemble_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
+    'dl_ensemble_data_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int32, _c_int32_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32, ctypes.c_double, ctypes.c_double]),
+    'dl_ensemble_data_destroy': (None, [ctypes.c_void_p]),
+    'dl_ensemble_data_set_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.c_void_p]),
+    'dl_ensemble_data_run': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_ensemble_data_get_state': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
+    'dl_ensemble_data_set_counter': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
+    'dl_ensemble_data_info': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p]),
     'dl_mh_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_double, ctypes.c_uint64, ctypes.c_double, ctypes.c_int64]),
     'dl_mh_destroy': (None, [ctypes.c_void_p]),
@@ -199,6 +206,11 @@ def _ptr(array):
 
 def _seed(seed):
     return ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _seeds(seeds):
+    """64-bit keys as a contiguous uint64 array (through Python integers: NumPy makes float64 of a list that mixes keys below and above 2^63)."""
+    return np.ascontiguousarray([int(seed) & 0xFFFFFFFFFFFFFFFF for seed in np.ravel(np.asarray(seeds, dtype=object))], dtype=np.uint64)
 
 
 def _refuse_expand(ctx, does='sampler moves'):
@@ -789,6 +801,60 @@ class DeviceEnsemble(_Handle):
         coords, logp = np.empty((self.nwalkers, self.n_params), dtype='f8'), np.empty(self.nwalkers, dtype='f8')
         nacc = np.empty(self.nwalkers, dtype='i8')
         self._check(self._lib.dl_ensemble_get_state(self._handle, _f64_ptr(coords), _f64_ptr(logp), _ptr(nacc), self._stream(stream)))
+        return coords, logp, nacc
+
+
+class DeviceEnsembleData(_Handle):
+    """Owner of one ``dl_ensemble_data`` (include/desilike_amd.h): ``len(data_index)`` ensembles of ``nwalkers`` walkers resident on the GPU of ``ctx``, ensemble e sampling
+    the posterior given data vector ``data_index[e]`` of the context's data batch with the draws of key ``seeds[e]``, all advancing in lockstep.  The arrays of
+    :class:`DeviceEnsemble` with a leading ensemble axis."""
+    _prefix = 'dl_ensemble_data'
+
+    def __init__(self, ctx, data_index, seeds, nwalkers, a=2., offset=0.):
+        _refuse_expand(ctx, 'ensembles propose')
+        data_index = np.ascontiguousarray(data_index, dtype='i4').ravel()
+        seeds = _seeds(seeds)
+        if seeds.shape != data_index.shape: raise ValueError('provide one seed per ensemble')
+        self._create(ctx._handle, int(data_index.size), _i32_ptr(data_index), seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(nwalkers), float(a), float(offset))
+        self._ctx = ctx   # (the context must outlive the ensembles)
+        self.n_ensembles, self.nwalkers, self.n_params, self.device = int(data_index.size), int(nwalkers), ctx.n_params, ctx.device
+        self.data_index, self.seeds = data_index, seeds
+
+    def set_state(self, coords, logposterior=None, stream=None):
+        shape = (self.n_ensembles, self.nwalkers, self.n_params)
+        coords = np.ascontiguousarray(coords, dtype='f8')
+        if coords.shape != shape: raise ValueError('coords must have shape {}, found {}'.format(shape, coords.shape))
+        if logposterior is not None:
+            logposterior = np.ascontiguousarray(logposterior, dtype='f8')
+            if logposterior.shape != shape[:2]: raise ValueError('logposterior must have shape {}'.format(shape[:2]))
+        self._check(self._lib.dl_ensemble_data_set_state(self._handle, _f64_ptr(coords), _f64_ptr(logposterior), self._stream(stream)))
+
+    def set_counter(self, iteration, naccepted=None, stream=None):
+        """Resume: the shared iteration counter of the counter-based generators (and accepted counts per ensemble and walker)."""
+        if naccepted is not None:
+            naccepted = np.ascontiguousarray(naccepted, dtype='i8')
+            if naccepted.shape != (self.n_ensembles, self.nwalkers): raise ValueError('naccepted must have shape {}'.format((self.n_ensembles, self.nwalkers)))
+        self._check(self._lib.dl_ensemble_data_set_counter(self._handle, int(iteration), _ptr(naccepted), self._stream(stream)))
+
+    def run(self, niterations, thin_by=1, chain=None, chain_logp=None, stream=None):
+        """Enqueue ``niterations`` updates of every ensemble (asynchronous); ``chain [niterations // thin_by, E, nwalkers, P]`` / ``chain_logp [niterations // thin_by, E,
+        nwalkers]``: float64 device tensors receiving the ensembles after every ``thin_by``-th update (optional)."""
+        import torch
+        nrec = int(niterations) // int(thin_by)
+
+        def ptr(tensor, shape):
+            if tensor is None: return None
+            assert tensor.is_cuda and tensor.is_contiguous() and tensor.dtype == torch.float64 and tuple(tensor.shape) == shape, (tensor.shape, shape)
+            return ctypes.c_void_p(tensor.data_ptr())
+
+        self._check(self._lib.dl_ensemble_data_run(self._handle, int(niterations), int(thin_by), ptr(chain, (nrec, self.n_ensembles, self.nwalkers, self.n_params)),
+                                                   ptr(chain_logp, (nrec, self.n_ensembles, self.nwalkers)), self._stream(stream)))
+
+    def get_state(self, stream=None):
+        """(coords [E, nwalkers, P], logposterior [E, nwalkers], naccepted [E, nwalkers]) as numpy arrays; synchronises the stream."""
+        shape = (self.n_ensembles, self.nwalkers, self.n_params)
+        coords, logp, nacc = np.empty(shape, dtype='f8'), np.empty(shape[:2], dtype='f8'), np.empty(shape[:2], dtype='i8')
+        self._check(self._lib.dl_ensemble_data_get_state(self._handle, _f64_ptr(coords), _f64_ptr(logp), _ptr(nacc), self._stream(stream)))
         return coords, logp, nacc
 
 

@@ -20,59 +20,7 @@
 #include <stdint.h>
 
 #include "dl_finalize_part.h"
-#include "dl_philox.h"   // dl_philox4x32, dl_uniform53
-
-enum { DL_ENS_STREAM_PERM = 0, DL_ENS_STREAM_MOVE = 1, DL_ENS_STREAM_ACCEPT = 3 };   // + half-step for the last two
-
-// Random split of the ensemble into two halves: position r holds walker F(r), F a keyed bijection of [0, nw) -- four rounds of (odd multiplier, offset) mod 2^m
-// and a right xor-shift, m = bit length of nw - 1, keyed by eight Philox words of the iteration, cycle-walked back into [0, nw).  Every element is a pure function
-// of (seed, iteration, r): nothing is ranked, stored or exchanged; the keys of a launch are made on the host and travel in the kernel arguments.
-// samplers.py CounterRNG.permutation is the NumPy statement of the same map.  F is inverted round by round (the xor-shift by >= m / 2 bits is an involution, the
-// multipliers are odd: their inverses mod 2^32 are made on the host), cycle-walking the inverse: position of walker w = F^-1(w).
-struct DlEnsSplit {
-    uint32_t mul[4], add[4], inv[4], mask, shift, nw;
-};
-
-inline DlEnsSplit dl_ens_split(long long iteration, int nw, uint32_t k0, uint32_t k1) {
-    const DlPhilox ka = dl_philox4x32((uint32_t)iteration, (uint32_t)((unsigned long long)iteration >> 32), 0u, DL_ENS_STREAM_PERM, k0, k1);
-    const DlPhilox kb = dl_philox4x32((uint32_t)iteration, (uint32_t)((unsigned long long)iteration >> 32), 1u, DL_ENS_STREAM_PERM, k0, k1);
-    DlEnsSplit f;
-    int m = 1;
-    while (m < 31 && (1u << m) < (uint32_t)nw) ++m;
-    for (int round = 0; round < 4; ++round) {
-        f.mul[round] = ka.x[round] | 1u; f.add[round] = kb.x[round];
-        uint32_t inv = f.mul[round];                      // Newton: x <- x (2 - a x) doubles the number of correct low bits (3 to start with: a a = 1 mod 8)
-        for (int it = 0; it < 5; ++it) inv *= 2u - f.mul[round] * inv;
-        f.inv[round] = inv;
-    }
-    f.mask = (1u << m) - 1u; f.shift = (uint32_t)(m + 1) / 2; f.nw = (uint32_t)nw;
-    return f;
-}
-
-__device__ __forceinline__ int dl_ens_split_at(const DlEnsSplit& f, int r) {
-    uint32_t x = (uint32_t)r;
-    do {
-#pragma unroll
-        for (int round = 0; round < 4; ++round) {
-            x = (x * f.mul[round] + f.add[round]) & f.mask;
-            x ^= x >> f.shift;
-        }
-    } while (x >= f.nw);
-    return (int)x;
-}
-
-// position r with dl_ens_split_at(f, r) == w
-__device__ __forceinline__ int dl_ens_split_inv(const DlEnsSplit& f, int w) {
-    uint32_t x = (uint32_t)w;
-    do {
-#pragma unroll
-        for (int round = 3; round >= 0; --round) {
-            x ^= x >> f.shift;
-            x = ((x - f.add[round]) * f.inv[round]) & f.mask;
-        }
-    } while (x >= f.nw);
-    return (int)x;
-}
+#include "dl_ens_draw.h"   // DL_ENS_STREAM_*, DlEnsSplit, dl_ens_split / _at / _inv, dl_philox4x32, dl_uniform53
 
 // What decides the accepts of the pending half-step (immutable while the launches that read it run)
 struct DlEnsPending {

@@ -23,7 +23,7 @@
 #include "dl_kernels.h"
 #include "dl_sampler_dev.h"   // dl_fail, DL_HIP_CHECK
 #include "dl_finalize_part.h"
-#include "dl_ens_fold.h"
+#include "dl_ens_fold.h"     // dl_ens_draw.h: dl_ens_draw_accept, dl_ens_draw_move, dl_ens_stage
 #include "dl_scalar_prefetch.h"
 
 namespace {
@@ -50,42 +50,6 @@ struct DlEnsArgs {
     DlEnsSplit split_acc, split_prop;   // the splits of those two iterations
     unsigned long long* stamps;         // DL_ENS_STAMPS diagnostics (nullptr in production): time spent per phase, summed over the launches (100 MHz clock), [7] = launches
 };
-
-// draws of slot j of the half-step to accept: walker and log(u); of the half-step to propose: walker, partner, z and (P - 1) log z
-// (emcee moves/red_blue.py, moves/stretch.py: z ~ g(z) on [1/a, a], partner from the complementary half)
-__device__ __forceinline__ void dl_ens_draw_accept(const DlEnsArgs& s, int j, int half, int& i, double& logu) {
-#pragma clang fp contract(off)
-    i = dl_ens_split_at(s.split_acc, s.half_acc * half + j);
-    const DlPhilox r = dl_philox4x32((uint32_t)s.it_acc, (uint32_t)((unsigned long long)s.it_acc >> 32), (uint32_t)j, DL_ENS_STREAM_ACCEPT + s.half_acc, s.k0, s.k1);
-    logu = log(dl_uniform53(r.x[0], r.x[1]));
-}
-
-__device__ __forceinline__ void dl_ens_draw_move(const DlEnsArgs& s, int j, int half, int& is, int& ic, double& zz, double& factor) {
-#pragma clang fp contract(off)
-    const DlPhilox r = dl_philox4x32((uint32_t)s.it_prop, (uint32_t)((unsigned long long)s.it_prop >> 32), (uint32_t)j, DL_ENS_STREAM_MOVE + s.half_prop, s.k0, s.k1);
-    const double u = dl_uniform53(r.x[0], r.x[1]);
-    const double t = (s.a - 1.) * u + 1.;
-    zz = (t * t) / s.a;
-    factor = (s.P - 1.) * log(zz);
-    ic = dl_ens_split_at(s.split_prop, (1 - s.half_prop) * half + (int)(r.x[2] % (uint32_t)half));
-    is = dl_ens_split_at(s.split_prop, s.half_prop * half + j);
-}
-
-// asynchronous copy of n doubles (16-byte aligned source) into LDS: 16-byte LDS-DMA chunks (global_load_lds_dwordx4: no registers, nothing waits until the
-// workgroup's barrier), lane l of a wavefront writes chunk l of the wavefront's 1 KB slot.  rot_c > 0: rows of rot_c chunks, chunk c of row r lands at position
-// (c + r) % rot_c of the row (threads that walk their own row chunk by chunk then spread over the LDS banks instead of all hitting the same two).
-__device__ __forceinline__ void dl_ens_stage(double* dst, const double* __restrict__ src, int n, int rot_c, int wave, int lane, int nthr) {
-    const int chunks = n >> 1;
-    for (int c0 = wave * 64; c0 < chunks; c0 += nthr) {
-        const int slot = c0 + lane;
-        if (slot < chunks) {
-            int from = slot;
-            if (rot_c > 0) { const int r = slot / rot_c, cp = slot - r * rot_c; int c = cp - r % rot_c; if (c < 0) c += rot_c; from = r * rot_c + c; }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 2 * (size_t)from), (__attribute__((address_space(3))) void*)(dst + 2 * (size_t)c0), 16, 0, 0);
-        }
-    }
-    if ((n & 1) && wave == 0 && lane == 0) dst[n - 1] = src[n - 1];
-}
 
 // One workgroup: the ensemble is a few hundred walkers x <= 64 parameters.  Everything the launch reads -- positions, log-posteriors, the pending proposals, their
 // partial chi2 and the prior table -- is requested at the top as LDS-DMA (one round trip for all of it; with register loads in run-time loops every loop iteration
@@ -267,10 +231,10 @@ size_t dl_ens_shared_bytes(int nw, int P, int n_tiles) {
 void dl_ens_launch(const DlEnsArgs& s_in, hipStream_t stream) {
     const int n_tiles = s_in.part != nullptr ? s_in.n_tiles : 0;
     DlEnsArgs s = s_in;
-    s.stage_parts = n_tiles > 0 && n_tiles % 8 == 0 && dl_ens_shared_bytes(s.nw, s.P, n_tiles) <= 144 * 1024;   // (the staged rows are walked in groups of four 16-byte chunks)
+    s.stage_parts = n_tiles > 0 && n_tiles % 8 == 0 && dl_ens_shared_bytes(s.nw, s.P, n_tiles) <= DL_ENS_LDS_BUDGET;   // (the staged rows are walked in groups of four 16-byte chunks)
     const size_t shm = dl_ens_shared_bytes(s.nw, s.P, s.stage_parts ? n_tiles : 0);
     const bool force_global = dl_options().ens_global;   // (tests: the global-memory variant on a small ensemble)
-    if (shm <= 144 * 1024 && !force_global) {
+    if (shm <= DL_ENS_LDS_BUDGET && !force_global) {
         // up to 512 walkers: 512 threads (one slot per thread in either phase); beyond: 1024 threads
         if (s.nw <= 512) {
             if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)dl_ensemble_step_lds_kernel<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);

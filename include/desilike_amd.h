@@ -374,6 +374,32 @@ int  dl_ensemble_set_counter(dl_ensemble* ens, int64_t iteration, const int64_t*
 /* integer properties: "nwalkers", "n_params", "iteration", "rank", "world", "rows_per_rank" */
 int64_t dl_ensemble_info(const dl_ensemble* ens, const char* key);
 
+/* ---- many device-resident ensembles, one per data vector of the data batch ("sample every mock") ---------------------------------------
+ * ``n_ensembles`` independent ensembles of ``nwalkers`` walkers (the stretch move of dl_ensemble), ensemble e bound to data vector data_index[e] of the context's
+ * data batch (dl_data_set / dl_data_set_solved; repeats allowed, any order, data vectors may go unused) and keyed by seeds[e], advancing in lockstep on one
+ * iteration counter: per half-step ONE step kernel of n_ensembles workgroups (accept the previous half, draw the split, stretch proposals; the state of an
+ * ensemble in the LDS of its workgroup) and ONE paired dl_eval_logposterior_data of n_ensembles * nwalkers / 2 rows, rows e * nwalkers / 2 .. (e + 1) * nwalkers / 2 - 1
+ * those of ensemble e; nothing synchronises with the host.  The draws of ensemble e are those of a dl_ensemble created with seed seeds[e].  Log-posterior
+ * conventions of dl_ensemble: NaN -> -inf, then + ``offset`` (the constant of a posterior context marginalised once over linear parameters); contexts with solved
+ * parameters given their batch through dl_data_set_solved work unchanged.  One rank.
+ * dl_ensemble_data_create returns 1 (message in dl_last_error(NULL)), before any device call, for a context without a data batch, an index outside
+ * [0, n_data_batch), nwalkers odd, < 2 or > 8192, a <= 1, and for (nwalkers, P) whose state -- (3 nwalkers P / 2 + nwalkers + 2) doubles -- exceeds the 144 KB of LDS
+ * a step workgroup may hold (an ensemble that large is better served by one dl_ensemble per data vector).
+ * dl_data_set replaces the batch in place: the ensembles keep their indices, so create them again after it; dl_ensemble_data_run checks "n_data_batch" against
+ * the indices at every call and returns 1 if they no longer fit.
+ * Arrays are those of dl_ensemble with a leading ensemble axis: coords [E, nwalkers, P], logposterior [E, nwalkers] (NULL: evaluated at the next run, every walker
+ * against its ensemble's data vector), naccepted [E, nwalkers]; chain_dev [niterations / thin_by, E, nwalkers, P], chain_logp_dev [niterations / thin_by, E, nwalkers]. */
+typedef struct dl_ensemble_data dl_ensemble_data;
+int  dl_ensemble_data_create(dl_ensemble_data** out, dl_ctx* ctx, int32_t n_ensembles, const int32_t* data_index /* host [E] */, const uint64_t* seeds /* host [E] */,
+                             int32_t nwalkers, double a, double offset);
+void dl_ensemble_data_destroy(dl_ensemble_data* ens);
+int  dl_ensemble_data_set_state(dl_ensemble_data* ens, const double* coords, const double* logposterior, void* hip_stream);
+int  dl_ensemble_data_run(dl_ensemble_data* ens, int64_t niterations, int32_t thin_by, double* chain_dev, double* chain_logp_dev, void* hip_stream);
+int  dl_ensemble_data_get_state(dl_ensemble_data* ens, double* coords, double* logposterior, int64_t* naccepted, void* hip_stream);
+int  dl_ensemble_data_set_counter(dl_ensemble_data* ens, int64_t iteration, const int64_t* naccepted, void* hip_stream);
+/* integer properties: "n_ensembles", "nwalkers", "n_params", "iteration", "lds_bytes" (of a step workgroup) */
+int64_t dl_ensemble_data_info(const dl_ensemble_data* ens, const char* key);
+
 /* ---- device-resident blocked Metropolis-Hastings sampler ----------------------------------------------------------------------------------
  * The reference's own MCMC (desilike/samplers/mcmc.py: MHSampler 25-127, BlockProposer 199-328 -- the CosmoMC / cobaya fast-slow blocked proposal: cycle through
  * the columns of a random rotation of every block, radial scale from a mixture, jump = Cholesky factor of the proposal covariance x direction), with ``nchains``

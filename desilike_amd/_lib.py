@@ -35,6 +35,8 @@ SYMBOLS = {
     'dl_data_set': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int32]),
     'dl_data_set_solved': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int32]),
     'dl_eval_solved_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_sample_solved_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_logposterior_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_fisher_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_fisher_analytic': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -670,6 +672,52 @@ class Context(_Handle):
         out, solved = self.eval_solved_data(th, torch.as_tensor(index, device=device), status=status)
         torch.cuda.synchronize(device)
         return out.cpu().numpy(), status.cpu().numpy(), solved.cpu().numpy()
+
+    def sample_solved_data(self, theta, index, index0=0, size=1, seed=42, stream=None):
+        """:meth:`sample_solved` against the data batch (``dl_sample_solved_data``): posterior draws of the analytically solved parameters of point b of
+        ``theta [B, n_params]`` given data vector ``index[b]`` (``index [B]`` int32) -> ``(solved [B, size, n_solved], loglike [B, size], logprior [B, size],
+        status [B])``; loglike + logprior is the un-marginalised log-posterior at (theta, draw) against that data vector; NaN where ``status`` is not 0.  A draw is a
+        pure function of (seed, index0 + row, draw, component): not of ``index``.  ``theta`` and ``index``: device tensors (device tensors are returned, asynchronous
+        on ``stream``) or arrays (arrays are returned).  ``ValueError``, before any device call: ``size < 1``, ``index0 < 0``, no analytically solved parameter,
+        ``index`` not B 32-bit integers."""
+        import torch
+        size, index0, seed = int(size), int(index0), int(seed) & 0xFFFFFFFFFFFFFFFF
+        if size < 1:
+            raise ValueError('sample_solved_data: size must be at least 1, found {:d}'.format(size))
+        if index0 < 0:
+            raise ValueError('sample_solved_data: index0 must not be negative')
+        if self.n_solved == 0:
+            raise ValueError('sample_solved_data: the context has no analytically solved parameter')
+        host = not torch.is_tensor(theta)
+        if host:
+            theta = np.ascontiguousarray(np.atleast_2d(theta), dtype='f8')
+        B, ns = theta.shape[0], self.n_solved
+        if torch.is_tensor(index):
+            index_ok = index.dtype == torch.int32 and tuple(index.shape) == (B,) and index.is_contiguous()
+        else:
+            index = np.asarray(index)
+            index_ok = index.dtype == np.int32 and index.shape == (B,)
+        if not index_ok:
+            raise ValueError('sample_solved_data: index must be {:d} contiguous 32-bit integers, found shape {} and type {}'.format(B, tuple(index.shape), index.dtype))
+        device = torch.device('cuda', self.device)
+        if host:
+            theta = torch.as_tensor(theta, device=device)
+        if not torch.is_tensor(index):
+            index = torch.as_tensor(np.ascontiguousarray(index), device=device)
+        if stream is None:
+            stream = torch.cuda.current_stream(device).cuda_stream
+        theta = self._device_theta(theta, stream)
+        solved = torch.empty((B, size, ns), dtype=torch.float64, device=device)
+        loglike, logprior = torch.empty((B, size), dtype=torch.float64, device=device), torch.empty((B, size), dtype=torch.float64, device=device)
+        status = torch.empty(B, dtype=torch.int32, device=device)
+        if B:
+            self._check(self._lib.dl_sample_solved_data(self._handle, ctypes.c_void_p(theta.data_ptr()), B, ctypes.c_void_p(index.data_ptr()), index0, size, seed,
+                                                        ctypes.c_void_p(solved.data_ptr()), ctypes.c_void_p(loglike.data_ptr()), ctypes.c_void_p(logprior.data_ptr()),
+                                                        ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(stream)))
+        if host:
+            torch.cuda.synchronize(device)
+            return tuple(t.cpu().numpy() for t in (solved, loglike, logprior, status))
+        return solved, loglike, logprior, status
 
     def eval_fisher_data(self, centers, steps, index, hessian=None, gradient=None, offset=None, stream=None):
         """:meth:`eval_fisher` with the residual of centre b taken against data vector ``index[b]`` of the data batch (``dl_eval_fisher_data``; ``index`` int32 device

@@ -16,6 +16,7 @@
 #include "dl_ens_fold.h"
 #include "dl_prior.h"
 #include "dl_sample_solved.h"
+#include "dl_sample_solved_data.h"
 #include "dl_data_batch.h"
 #include "dl_data_batch_marg.h"
 
@@ -658,6 +659,15 @@ struct DlDataEval {
     const int32_t* index;   // [B] device, or null: every data vector (out [B, M])
     double* out;
     double* solved;         // [B, n_solved] device, or null (dl_eval_solved_data: paired calls on a context with solved parameters)
+    const struct DlDataDraw* draw = nullptr;   // dl_sample_solved_data: the draw kernel takes the place of the paired kernel (index set, out / solved unused)
+};
+
+// the draws of dl_sample_solved_data (dl_sample_solved_data.h): outputs [B, size, n_solved], [B, size], [B, size]; index0: global index of row 0 of the call
+struct DlDataDraw {
+    int64_t index0;
+    int32_t size;
+    uint64_t seed;
+    double *solved, *loglike, *logprior;
 };
 
 // workspaces of the data-batch finalize of a context with solved parameters: grown like those of dl_reserve, never on the hot path after the first call of a shape
@@ -818,7 +828,13 @@ static int dl_eval_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, double*
                                         stream, ctx->n_white);
         }
         prof_phase(2);
-        if (data && ctx->n_solved > 0)   // per-point records, then the solve of every pair (dl_data_batch_marg.h)
+        if (data && ctx->n_solved > 0 && data->draw) {   // per-point records, then the draws of every pair (dl_sample_solved_data.h); the pass offset advances index0
+            const DlDataDraw& dr = *data->draw;
+            dl_launch_data_marg_points(ctx->delta_ws, ctx->N_pad, ctx->n_white, R, n_slabs, slab_stride, ctx->marg, th, P, ctx->priors_dev, nb, ctx->dbm_rows, ctx->dbm_rec, stream);
+            dl_launch_data_marg_draw(ctx->marg, ctx->dbm_rows, ctx->N_pad, ctx->n_white, R, ctx->dbm_rec, ctx->data_bias_dev, ctx->N_pad, ctx->n_data_batch, data->index + b0, nb,
+                                     dr.index0 + b0, dr.size, dr.seed, dr.solved + (size_t)b0 * dr.size * ctx->n_solved, dr.loglike + (size_t)b0 * dr.size,
+                                     dr.logprior + (size_t)b0 * dr.size, status_dev ? status_dev + b0 : nullptr, stream);
+        } else if (data && ctx->n_solved > 0)   // per-point records, then the solve of every pair (dl_data_batch_marg.h)
             dl_launch_data_marg(ctx->delta_ws, ctx->N_pad, ctx->n_white, R, n_slabs, slab_stride, ctx->marg, ctx->data_bias_dev, ctx->N_pad, ctx->n_data_batch,
                                 data->index ? data->index + b0 : nullptr, th, P, ctx->priors_dev, nb, ctx->dbm_rows, ctx->dbm_rec,
                                 data->out + (size_t)b0 * (data->index ? 1 : ctx->n_data_batch), status_dev ? status_dev + b0 : nullptr,
@@ -1039,6 +1055,24 @@ int dl_eval_solved_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const i
     DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (dl_dbm_reserve(ctx, B)) return 1;
     const DlDataEval data = {data_index_dev, out_dev, solved_dev};
+    return dl_eval_impl(ctx, theta_dev, B, nullptr, nullptr, nullptr, status_dev, nullptr, hip_stream, 1, nullptr, &data);
+}
+
+// Posterior draws of the solved parameters of point b given data vector data_index_dev[b] (dl_sample_solved_data.h): the residual route and the point kernel of
+// dl_eval_solved_data -- same passes over B, same workspaces --, then the draw kernel in the place of the paired kernel.
+int dl_sample_solved_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, int64_t index0, int32_t size, uint64_t seed, double* solved_dev,
+                          double* loglike_dev, double* logprior_dev, int32_t* status_dev, void* hip_stream) {
+    if (!ctx) { g_last_error = "dl_sample_solved_data: null context"; return 1; }
+    if (ctx->n_data_batch == 0) return dl_fail(ctx, "dl_sample_solved_data: the context has no data batch (dl_data_set_solved)");
+    if (ctx->n_solved == 0) return dl_fail(ctx, "dl_sample_solved_data: no analytically solved parameter in this likelihood");
+    if (size < 1) return dl_fail(ctx, "dl_sample_solved_data: size must be at least 1");
+    if (index0 < 0) return dl_fail(ctx, "dl_sample_solved_data: index0 must not be negative");
+    if (B > 0 && (!data_index_dev || !solved_dev || !loglike_dev || !logprior_dev)) return dl_fail(ctx, "dl_sample_solved_data: null data index or output");
+    if (B <= 0) return B == 0 ? 0 : dl_fail(ctx, "dl_sample_solved_data: invalid batch");
+    DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (dl_dbm_reserve(ctx, B)) return 1;
+    const DlDataDraw draw = {index0, size, seed, solved_dev, loglike_dev, logprior_dev};
+    const DlDataEval data = {data_index_dev, nullptr, nullptr, &draw};
     return dl_eval_impl(ctx, theta_dev, B, nullptr, nullptr, nullptr, status_dev, nullptr, hip_stream, 1, nullptr, &data);
 }
 

@@ -155,11 +155,23 @@ inline bool dl_dbm_point_host(const double* const* t_rows, int n, int n_s, const
 }
 
 #if defined(__HIPCC__)
-struct DlMargDev;
+#include "dl_kernels.h"
 // out: [B, M] (index == nullptr: cross) or [B] (paired); solved [B, n_s] (paired only, may be null); rows_ws [B, rows_per_point, ld], rec_ws [B, DL_DBM_REC]
 void dl_launch_data_marg(const double* dtilde, int64_t ld, int n, int rows_per_point, int n_slabs, int64_t slab_stride, const DlMargDev& mg, const double* bias_tab, int64_t ldb,
                          int M, const int32_t* index, const double* theta, int n_params, const double* priors, int64_t B, double* rows_ws, double* rec_ws, double* out,
                          int32_t* status, double* solved, hipStream_t stream);
+// the point kernel alone (the first launch of dl_launch_data_marg): rows and records of the B points, for a consumer of its own (dl_sample_solved_data.h)
+void dl_launch_data_marg_points(const double* dtilde, int64_t ld, int n, int rows_per_point, int n_slabs, int64_t slab_stride, const DlMargDev& mg, const double* theta,
+                                int n_params, const double* priors, int64_t B, double* rows_ws, double* rec_ws, hipStream_t stream);
+
+// row of solved parameter s of point b: its point-dependent row in the row workspace, or the constant one (shared by the pair kernels and by the draw kernel of
+// dl_sample_solved_data.hip, whose row phase must stay the paired kernel's)
+__device__ __forceinline__ const double* dl_dbm_trow(const DlMargDev& mg, int s, const double* __restrict__ rows_ws, int64_t b, int rows_per_point, int64_t ld) {
+    int vs = -1;
+#pragma unroll
+    for (int q = 0; q < DL_MAX_SOLVED; ++q) if (q == s) vs = mg.var_slot[q];
+    return vs >= 0 ? rows_ws + ((size_t)b * rows_per_point + 1 + vs) * ld : mg.tconst + (size_t)s * ld;
+}
 #endif
 
 #if defined(__HIPCC__) && defined(DL_DBM_KERNELS)   // (dl_kernels.hip: after dl_wave_sum, dl_grouplane, dl_lane_cholesky)
@@ -283,14 +295,6 @@ __device__ __forceinline__ double dl_dbm_logposterior(double ll, double lps, con
     else if (lp == -inf) st = DL_ST_OUT_OF_PRIOR;
     else if ((flags & 2) || !(ll == ll) || ll == inf || ll == -inf) st = DL_ST_NONFINITE;
     return st == DL_ST_OK ? ll + (lp + lps) : -inf;
-}
-
-// row of solved parameter s of point b: its point-dependent row in the row workspace, or the constant one
-__device__ __forceinline__ const double* dl_dbm_trow(const DlMargDev& mg, int s, const double* __restrict__ rows_ws, int64_t b, int rows_per_point, int64_t ld) {
-    int vs = -1;
-#pragma unroll
-    for (int q = 0; q < DL_MAX_SOLVED; ++q) if (q == s) vs = mg.var_slot[q];
-    return vs >= 0 ? rows_ws + ((size_t)b * rows_per_point + 1 + vs) * ld : mg.tconst + (size_t)s * ld;
 }
 
 // ---- cross: out[b, m] for a tile of TB = 2 TBX points x TM = 2 (256 / TBX) data vectors; thread (tb, tm) owns the 2 x 2 pairs (2 tb + {0, 1}, 2 tm + {0, 1}) ----------------
@@ -441,13 +445,18 @@ static void dl_dbm_launch_pairs(const DlMargDev& mg, const DlDbmConst& kc, const
                   mg, kc, bias_tab, ldb, M, B, out, status);
 }
 
+void dl_launch_data_marg_points(const double* dtilde, int64_t ld, int n, int rows_per_point, int n_slabs, int64_t slab_stride, const DlMargDev& mg, const double* theta,
+                                int n_params, const double* priors, int64_t B, double* rows_ws, double* rec_ws, hipStream_t stream) {
+    const size_t shm = ((size_t)(1 + mg.n_s) * ((n + 7) & ~7) + 512) * sizeof(double);   // <= 17 x 512 + 512 doubles = 73 728 B
+    if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)dl_dbm_point_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    DL_LAUNCH(dl_dbm_point_kernel, dim3((unsigned)B), dim3(64), shm, stream, dtilde, ld, n, rows_per_point, n_slabs, slab_stride, mg, theta, n_params, priors, B, rows_ws, rec_ws);
+}
+
 void dl_launch_data_marg(const double* dtilde, int64_t ld, int n, int rows_per_point, int n_slabs, int64_t slab_stride, const DlMargDev& mg, const double* bias_tab, int64_t ldb,
                          int M, const int32_t* index, const double* theta, int n_params, const double* priors, int64_t B, double* rows_ws, double* rec_ws, double* out,
                          int32_t* status, double* solved, hipStream_t stream) {
     const int ns = mg.n_s;
-    const size_t shm = ((size_t)(1 + ns) * ((n + 7) & ~7) + 512) * sizeof(double);   // <= 17 x 512 + 512 doubles = 73 728 B
-    if (shm > 48 * 1024) (void)hipFuncSetAttribute((const void*)dl_dbm_point_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    DL_LAUNCH(dl_dbm_point_kernel, dim3((unsigned)B), dim3(64), shm, stream, dtilde, ld, n, rows_per_point, n_slabs, slab_stride, mg, theta, n_params, priors, B, rows_ws, rec_ws);
+    dl_launch_data_marg_points(dtilde, ld, n, rows_per_point, n_slabs, slab_stride, mg, theta, n_params, priors, B, rows_ws, rec_ws, stream);
     DlDbmConst kc;
     for (int s = 0; s < DL_MAX_SOLVED; ++s) { kc.x0[s] = s < ns ? mg.x0[s] : 0.; kc.loc[s] = s < ns ? mg.loc[s] : 0.; kc.prec[s] = s < ns ? mg.prec[s] : 0.; }
     auto launch = [&](auto tag) {

@@ -240,6 +240,23 @@ class DataBatch(object):
         values, index = self._check_values(values, index)
         return self.context.eval_solved_data_host(values, index)[2]
 
+    def sample_solved(self, values, index, index0=0, size=1, seed=42):
+        """``values [B, n_varied]``, ``index [B]`` (integers in ``[0, M)``) -> ``(solved [B, size, n_solved], loglikelihood [B, size], logprior [B, size], status [B])``:
+        ``size`` posterior draws of the analytically solved parameters of point b given data vector ``index[b]`` and the log-likelihood / log-prior with nothing
+        marginalised at every draw (``dl_sample_solved_data``; :func:`desilike_amd.sample_solved` treats whole chains).  ``index0``: global index of row 0 in its
+        chain -- a draw is a pure function of (seed, index0 + row, draw, component).  Batches made with ``solve='point'`` only."""
+        if self.solve != 'point':
+            raise ValueError("the solved parameters of a data batch are available with data_batch(data, solve='point')")
+        size, index0 = int(size), int(index0)
+        if size < 1:
+            raise ValueError('sample_solved: size must be at least 1, found {:d}'.format(size))
+        if index0 < 0:
+            raise ValueError('sample_solved: index0 must not be negative')
+        if index is None:
+            raise ValueError('index must be {:d} integers, found None'.format(np.atleast_2d(values).shape[0]))
+        values, index = self._check_values(values, index)
+        return self.context.sample_solved_data(values, index.astype('i4'), index0=index0, size=size, seed=seed)
+
 
 class ObservablesGaussianLikelihood(BaseGaussianLikelihood):
     """

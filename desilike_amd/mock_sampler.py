@@ -292,6 +292,26 @@ class MockEmceeSampler(BasePosteriorSampler):
         samples['logposterior'] = logp.ravel()
         return samples
 
+    def sample_solved(self, size=1, seed=42, burnin=0, data_batch=None):
+        """Posterior draws of the analytically solved parameters at every chain point, each chain against its own mock (:func:`desilike_amd.sample_solved` with a
+        data batch): a nested list shaped like ``chains`` of :class:`Samples` ``[niterations - burnin, nwalkers * size]`` -- every column repeated ``size`` times along
+        the last axis, the solved parameters as columns, ``loglikelihood`` / ``logprior`` / ``logposterior`` with nothing marginalised.  All chains are flattened into
+        one point list with a data index per point, in the order i, k, then the chain's own flattening -- that order is the global point index of the draws -- and
+        treated in chunked calls, not one call per mock.  ``data_batch``: a ``solve='point'`` batch over the same data, for a sampler that ran on a
+        ``solve='constant'`` batch (default: the sampler's own batch, which must then be a ``'point'`` one)."""
+        from .solved import check_point_batch, sample_solved_chains
+        size, burnin = int(size), int(burnin)
+        if size < 1:
+            raise ValueError('sample_solved: size must be at least 1, found {:d}'.format(size))
+        if data_batch is None:
+            data_batch = self.data_batch
+        elif data_batch.size != self.data_batch.size or data_batch.likelihood is not self.data_batch.likelihood:
+            raise ValueError('sample_solved: data_batch must hold the {:d} data vectors of the likelihood this sampler ran on'.format(self.data_batch.size))
+        check_point_batch(data_batch)
+        flat = [{name: value[burnin:] for name, value in chain.items()} for row in self.chains for chain in row]
+        new = sample_solved_chains(data_batch, flat, self.index, size=size, seed=seed)
+        return [[Samples(new[i * self.nchains + k]) for k in range(self.nchains)] for i in range(len(self.mocks))]
+
     def gelman_rubin(self, burnin=0):
         """``[len(mocks)]``: max eigenvalue of the Gelman-Rubin statistic - 1 across the chains of every mock (:func:`desilike_amd.diagnostics.gelman_rubin`)."""
         from . import diagnostics

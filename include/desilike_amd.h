@@ -239,6 +239,23 @@ int  dl_data_set_solved(dl_ctx* ctx, const double* flatdata, int32_t M);
  * Returns 1 without a data batch or on a context without solved parameters. */
 int  dl_eval_solved_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, double* out_dev, int32_t* status_dev, double* solved_dev,
                          void* hip_stream);
+/* Posterior draws of the analytically solved parameters of point b given data vector data_index_dev[b] of a batch set with dl_data_set_solved: dl_sample_solved for
+ * a data batch (csrc/dl_sample_solved_data.h).  The residual route and the point kernel of dl_eval_solved_data (same passes over B, same workspaces), then ONE
+ * kernel, one wavefront per point, in the place of the paired kernel: x^ = x0 + dx of the pair (the bits dl_eval_solved_data returns) and, for each of the ``size``
+ * draws, v = C^-T z with the point's factor C C^T = A = H + diag(1 / scale^2) (z standard Gaussians; covariance A^-1) and x = x^ + v.
+ *   solved_dev [B, size, n_solved] the draws x ('.marg' and '.best' parameters alike);
+ *   loglike_dev [B, size] = ll + (-1/2 (|z|^2 - sum_s v_s^2 / scale_s^2) + 1/2 logdet A[marg, marg]), ll the marginalised log-likelihood of the pair;
+ *   logprior_dev [B, size] = logprior of the point and of x^ - 1/2 sum_s v_s^2 / scale_s^2: the split of dl_sample_solved; their sum is the log-posterior at
+ *   (theta, x) against that data vector with NO parameter marginalised;
+ *   status_dev [B] (may be NULL): DL_STATUS_NAN_INPUT for an index outside [0, M) (the table is not read) or a NaN input, DL_STATUS_OUT_OF_PRIOR,
+ *   DL_STATUS_NONFINITE for a pivot of A that is not positive or a non-finite ll; such a point gets NaN draws and NaN values.
+ * Random draws: those of dl_sample_solved -- Philox4x32-10 keyed by ``seed``, counter (index lo, index hi, draw, 80 | pair << 8) with index = index0 + row,
+ * (n_solved + 1) / 2 Box-Muller pairs.  A draw is a pure function of (seed, index, draw, component): it does not depend on the data index, on M, on B, on ``size``
+ * or on how a chain is cut into calls (with the matching index0).  Returns 0 (B = 0: nothing launched); 1 -- before any launch -- without a data batch, on a
+ * context without solved parameters, for size < 1, index0 < 0, a NULL data index or a NULL output with B > 0.  Asynchronous on ``hip_stream``. */
+int  dl_sample_solved_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, int64_t index0, int32_t size, uint64_t seed,
+                           double* solved_dev /* [B, size, n_solved] */, double* loglike_dev /* [B, size] */, double* logprior_dev /* [B, size] */,
+                           int32_t* status_dev /* [B], may be NULL */, void* hip_stream);
 /* dl_eval_fisher with the residual of centre b taken against data vector data_index_dev[b] of the data batch: same stencil, outputs, conventions (no 1/2) and limits
  * (P <= 31, no solved parameter).  The Hessian does not depend on the data.  An index outside [0, M): NaN offset and gradient for that centre. */
 int  dl_eval_fisher_data(dl_ctx* ctx, const double* centers_dev, const double* steps_dev, int64_t B, const int32_t* data_index_dev, double* hessian_dev, double* gradient_dev,

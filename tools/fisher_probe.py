@@ -19,7 +19,7 @@ sys.path.insert(0, ROOT)
 def context_on_library(like, path):
     """A second device context of ``like`` bound to another build of the library (symbols that build lacks are left unbound).  ``Context`` takes the library from
     ``_lib.load()`` once, in its constructor, and keeps it in ``self._lib``: the module global is swapped for the duration of that constructor only, and the returned
-    context goes on calling the OTHER CDLL (which it keeps alive) for all of its methods.  Probe use only."""
+    context goes on calling the OTHER CDLL (which it keeps alive) for all of its methods.  ``like``: a likelihood, or a configuration (dict; device 0).  Probe use only."""
     from desilike_amd import _lib
     current = _lib.load()
     other = ctypes.CDLL(path)
@@ -27,6 +27,7 @@ def context_on_library(like, path):
         if hasattr(other, name): getattr(other, name).restype, getattr(other, name).argtypes = restype, argtypes
     _lib._lib = other
     try:
+        if isinstance(like, dict): return _lib.Context(like, device=0)
         return _lib.Context(like._spec({}, like._flatdata_list(), like._precision_input), device=like.device)
     finally:
         _lib._lib = current

@@ -40,6 +40,8 @@ SYMBOLS = {
     'dl_eval_logposterior_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_fisher_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_fisher_analytic': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_eval_fisher_analytic_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'dl_eval_logposterior_grad_data': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_theory': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'dl_eval_batch_host': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_int32_p, _c_double_p]),
     'dl_eval_tns_tables': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
@@ -763,6 +765,52 @@ class Context(_Handle):
         if rc == 2: return None
         self._check(rc)
         return tuple(outputs)
+
+    def eval_fisher_analytic_data(self, centers, index, hessian=None, gradient=None, offset=None, stream=None):
+        """:meth:`eval_fisher_analytic` with the residual of centre b taken against data vector ``index[b]`` of the data batch (``dl_eval_fisher_analytic_data``;
+        ``index`` int32 device tensor ``[B]``): exact derivative rows, one theory row per centre; the Hessian does not depend on ``index``.  Returns ``None`` outside
+        the scope of :meth:`eval_fisher_analytic` (the caller uses :meth:`eval_fisher_data`)."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(centers.device).cuda_stream
+        B, P = centers.shape
+        if self.expand is not None:
+            raise NotImplementedError('Fisher algebra with parameters derived by an expression: differentiate w.r.t. the device columns and apply the chain rule on the host')
+        assert P == self.n_params and centers.is_contiguous() and centers.dtype == torch.float64
+        assert index.is_contiguous() and index.dtype == torch.int32 and tuple(index.shape) == (B,)
+        outputs = []
+        for tensor, shape in [(hessian, (B, P, P)), (gradient, (B, P)), (offset, (B,))]:
+            if tensor is None: tensor = torch.empty(shape, dtype=torch.float64, device=centers.device)
+            if tensor is False: tensor = None
+            else: assert tensor.is_contiguous() and tensor.dtype == torch.float64 and tuple(tensor.shape) == shape
+            outputs.append(tensor)
+        rc = self._lib.dl_eval_fisher_analytic_data(self._handle, ctypes.c_void_p(centers.data_ptr()), B, ctypes.c_void_p(index.data_ptr()),
+                                                    *[None if tensor is None else ctypes.c_void_p(tensor.data_ptr()) for tensor in outputs], ctypes.c_void_p(stream))
+        if rc == 2: return None
+        self._check(rc)
+        return tuple(outputs)
+
+    def eval_logposterior_grad_data(self, theta, index, logposterior=None, grad=None, status=None, stream=None):
+        """:meth:`eval_logposterior_grad` of point b given data vector ``index[b]`` of the data batch (``dl_eval_logposterior_grad_data``; ``index`` int32 device
+        tensor ``[B]``).  Returns ``(logposterior [B], grad [B, P])``, or ``None`` outside the scope (the Kaiser branch of :meth:`eval_logposterior_grad`: the caller
+        differentiates :meth:`eval_logposterior_data` numerically)."""
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(theta.device).cuda_stream
+        if self.expand is not None:
+            return None      # parameters derived by an expression: chain rule through the expression is not implemented
+        B = theta.shape[0]
+        assert theta.is_contiguous() and theta.dtype == torch.float64 and theta.shape[1] == self.n_params
+        assert index.is_contiguous() and index.dtype == torch.int32 and tuple(index.shape) == (B,)
+        if logposterior is None: logposterior = torch.empty(B, dtype=torch.float64, device=theta.device)
+        if grad is None: grad = torch.empty((B, self.n_params), dtype=torch.float64, device=theta.device)
+        assert status is None or (status.is_contiguous() and status.dtype == torch.int32 and tuple(status.shape) == (B,))
+        rc = self._lib.dl_eval_logposterior_grad_data(self._handle, ctypes.c_void_p(theta.data_ptr()), B, ctypes.c_void_p(index.data_ptr()),
+                                                      ctypes.c_void_p(logposterior.data_ptr()), ctypes.c_void_p(grad.data_ptr()),
+                                                      None if status is None else ctypes.c_void_p(status.data_ptr()), ctypes.c_void_p(stream))
+        if rc == 2: return None
+        self._check(rc)
+        return logposterior, grad
 
     def profile_enable(self, every=1, only=None):
         """Attach HIP events to the kernels' dispatch packets on one ``eval_batch`` call out of ``every`` (0 / False: off); ``only``: 'theory' /

@@ -1093,7 +1093,27 @@ static int64_t dl_fisher_emu_per_pass(const dl_ctx* ctx) {
     return std::max<int64_t>(64, std::min<int64_t>(2048, ((int64_t)16 << 20) / per_centre) / 64 * 64);
 }
 
-static int dl_eval_fisher_analytic_emu(dl_ctx* ctx, const double* centers_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, hipStream_t stream) {
+// the Kaiser branch of dl_eval_fisher_analytic (and of dl_eval_fisher_analytic_data): the Jacobian kernels' scope and the LDS-resident Gram product
+static bool dl_fisher_kaiser_in_scope(const dl_ctx* ctx) {
+    return !ctx->feat_ok && !ctx->any_transform && ctx->n_solved == 0 && ctx->n_params <= 31 && dl_grad_applicable(ctx->obs_kernarg.data(), ctx->n_obs) &&
+           dl_fisher_waves(ctx->n_white, ctx->n_params, nullptr, nullptr) >= 1;
+}
+
+// Checked data indices (dl_data_index_kernel: -1 outside the table) of the rows [b0, b0 + nc) of a data-batch call of B rows: ONE launch per call, with its first
+// pass, where the workspace holds them all (B <= DL_CHUNK); pass by pass beyond
+static const int32_t* dl_data_checked(dl_ctx* ctx, const int32_t* index_dev, int64_t B, int64_t b0, int64_t nc, hipStream_t stream) {
+    if (B <= DL_CHUNK) {
+        if (b0 == 0) dl_launch_data_index(index_dev, B, ctx->n_data_batch, ctx->data_index_ws, stream);
+        return ctx->data_index_ws + b0;
+    }
+    dl_launch_data_index(index_dev + b0, nc, ctx->n_data_batch, ctx->data_index_ws, stream);
+    return ctx->data_index_ws;
+}
+
+// data_index_dev (dl_eval_fisher_analytic_data): the sum of the residual row of centre b starts from row data_index[b] of the data batch's table instead of the
+// context's own whitened bias; null: the launches of dl_eval_fisher_analytic
+static int dl_eval_fisher_analytic_emu(dl_ctx* ctx, const double* centers_dev, int64_t B, const int32_t* data_index_dev, double* hessian_dev, double* gradient_dev,
+                                       double* offset_dev, hipStream_t stream) {
     const int P = ctx->n_params, Np = ctx->N_pad;
     const DlObsDev& o = ctx->obs_kernarg[0];
     const int64_t R = 1 + dl_emu_jac_n_xv(o), K = (int64_t)DL_FG_NM * Np;
@@ -1119,6 +1139,10 @@ static int dl_eval_fisher_analytic_emu(dl_ctx* ctx, const double* centers_dev, i
         const double* th = centers_dev + (size_t)b0 * P;
         dl_launch_emu_jac_tangent(o, th, P, nc, ctx->ej_basis, ctx->ej_c, ctx->ej_dc, stream);
         dl_launch_emu_grad_u(ctx->ej_basis, o.nb_pad, 0, o.nb_pad, ctx->gfrag_dev[0], ctx->ej_u, Np, Np, nc * R, stream);
+        if (data_index_dev)
+            dl_launch_emu_jac_rows(o, ctx->ej_u, Np, ctx->ej_c, ctx->ej_dc, ctx->data_bias_dev, P, ctx->n_white, Np, ctx->ej_resid, Np, ctx->ej_rows, Np, nc, stream,
+                                   dl_data_checked(ctx, data_index_dev, B, b0, nc, stream), Np);
+        else
         dl_launch_emu_jac_rows(o, ctx->ej_u, Np, ctx->ej_c, ctx->ej_dc, ctx->bias_white_dev, P, ctx->n_white, Np, ctx->ej_resid, Np, ctx->ej_rows, Np, nc, stream);
         dl_launch_fisher_rows(ctx->ej_resid, Np, ctx->ej_rows, Np, ctx->n_white, 1, 0, P, nc, hessian_dev ? hessian_dev + (size_t)b0 * P * P : nullptr,
                               gradient_dev ? gradient_dev + (size_t)b0 * P : nullptr, offset_dev ? offset_dev + b0 : nullptr, stream);
@@ -1127,19 +1151,23 @@ static int dl_eval_fisher_analytic_emu(dl_ctx* ctx, const double* centers_dev, i
     return 0;
 }
 
-int dl_eval_fisher_analytic(dl_ctx* ctx, const double* centers_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, void* hip_stream) {
-    if (!ctx) { g_last_error = "dl_eval_fisher_analytic: null context"; return 1; }
-    if (B < 0 || (B > 0 && !centers_dev)) return dl_fail(ctx, "dl_eval_fisher_analytic: invalid argument");
+// data_index_dev (dl_eval_fisher_analytic_data): the residual row of centre b is taken against vector data_index[b] of the data batch -- per pass the RESIDUAL route
+// of dl_eval_impl (tiled split-K window GEMM of the theory rows into delta_ws, no bias) and dl_data_resid_kernel (dl_data_batch.h) in the place of the chi2 GEMM with
+// the residual output; the Jacobian kernel, its window GEMM and the Gram kernel do not know.  Null: the launches of dl_eval_fisher_analytic.
+static int dl_eval_fisher_analytic_impl(dl_ctx* ctx, const double* centers_dev, int64_t B, const int32_t* data_index_dev, double* hessian_dev, double* gradient_dev,
+                                        double* offset_dev, void* hip_stream) {
+    const std::string fn = data_index_dev ? "dl_eval_fisher_analytic_data" : "dl_eval_fisher_analytic";   // (the entry point the messages name)
+    if (!ctx) { g_last_error = fn + ": null context"; return 1; }
+    if (B < 0 || (B > 0 && !centers_dev)) return dl_fail(ctx, fn + ": invalid argument");
     const int P = ctx->n_params, Np = ctx->N_pad, Kp = ctx->K_pad;
     // emulated: one observable on the feature path, MLP / Taylor engines, the solved parameters varied (dl_emu_jac.h)
     if (dl_fisher_emu_in_scope(ctx)) {
         if (B == 0) return 0;
         DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
         if (dl_order_streams(ctx, (hipStream_t)hip_stream)) return 1;
-        return dl_eval_fisher_analytic_emu(ctx, centers_dev, B, hessian_dev, gradient_dev, offset_dev, (hipStream_t)hip_stream);
+        return dl_eval_fisher_analytic_emu(ctx, centers_dev, B, data_index_dev, hessian_dev, gradient_dev, offset_dev, (hipStream_t)hip_stream);
     }
-    if (ctx->feat_ok || ctx->any_transform || ctx->n_solved != 0 || P > 31 || !dl_grad_applicable(ctx->obs_kernarg.data(), ctx->n_obs) ||
-        dl_fisher_waves(ctx->n_white, P, nullptr, nullptr) < 1) return 2;
+    if (!dl_fisher_kaiser_in_scope(ctx)) return 2;
     if (B == 0) return 0;
     hipStream_t stream = (hipStream_t)hip_stream;
     dl_prof_events.start = dl_prof_events.stop = nullptr;
@@ -1168,14 +1196,24 @@ int dl_eval_fisher_analytic(dl_ctx* ctx, const double* centers_dev, int64_t B, d
     for (int64_t b0 = 0; b0 < B; b0 += per_pass) {   // (no launch before every pass is known to fit the slab buffer: a retuned split policy is an error here, not an overflow)
         int cps = 0;
         const int64_t nr = std::min<int64_t>(per_pass, B - b0) * P;
-        if ((int64_t)dl_gemm_tiled_splits(nr, Np, Kp, &cps) * nr > ctx->fa_slab_rows) return dl_fail(ctx, "dl_eval_fisher_analytic: the split-K slabs of the window product exceed their buffer");
+        if ((int64_t)dl_gemm_tiled_splits(nr, Np, Kp, &cps) * nr > ctx->fa_slab_rows) return dl_fail(ctx, fn + ": the split-K slabs of the window product exceed their buffer");
     }
     for (int64_t b0 = 0; b0 < B; b0 += per_pass) {
         const int64_t nc = std::min<int64_t>(per_pass, B - b0), nr = nc * P;
         const double* th = centers_dev + (size_t)b0 * P;
+        if (data_index_dev) {
+            dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, th, P, nc, ctx->power_ws, Kp, nullptr, 0, stream, nullptr, 0, 0, ctx->obs_array_dev);
+            int cps_r = 0;
+            const int n_slabs_r = dl_gemm_tiled_splits(nc, Np, Kp, &cps_r);   // (nc <= the rows dl_reserve sized delta_ws for: its slab rule is this policy's)
+            const int64_t slab_stride_r = nc * (int64_t)Np;
+            dl_launch_window_gemm_tiled(ctx->power_ws, Kp, ctx->wt_white_dev, Kp, ctx->delta_ws, slab_stride_r, Np, nc, Np, Kp, n_slabs_r, cps_r, stream, ctx->n_white);
+            dl_launch_data_resid(ctx->delta_ws, Np, ctx->n_white, n_slabs_r, slab_stride_r, ctx->data_bias_dev, Np, dl_data_checked(ctx, data_index_dev, B, b0, nc, stream), nc, Np,
+                                 ctx->fa_resid, Np, stream);
+        } else {
         dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, th, P, nc, ctx->power_ws, Kp, nullptr, 0, stream, nullptr, 0, xcd_local ? dl_chi2_gemm_row_tile(nc, Np) : 0, ctx->obs_array_dev);
         dl_launch_chi2_gemm(ctx->power_ws, Kp, ctx->wt_white_dev, Kp, ctx->bias_white_dev, ctx->delta_ws, nc, Np, Kp, nullptr, nullptr, nullptr, nullptr, nullptr, 1, stream,
                             ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data(), ctx->K_live, ctx->fa_resid, Np, ctx->wt_frag_dev);
+        }
         dl_launch_fullshape_jac(ctx->obs_kernarg.data(), ctx->n_obs, ctx->obs_array_dev, th, P, nc, ctx->K_live, Kp, ctx->fa_jac, Kp, stream);
         int cps = 0;
         const int n_slabs = dl_gemm_tiled_splits(nr, Np, Kp, &cps);
@@ -1186,6 +1224,20 @@ int dl_eval_fisher_analytic(dl_ctx* ctx, const double* centers_dev, int64_t B, d
     }
     DL_HIP_CHECK(ctx, hipGetLastError());
     return 0;
+}
+
+int dl_eval_fisher_analytic(dl_ctx* ctx, const double* centers_dev, int64_t B, double* hessian_dev, double* gradient_dev, double* offset_dev, void* hip_stream) {
+    return dl_eval_fisher_analytic_impl(ctx, centers_dev, B, nullptr, hessian_dev, gradient_dev, offset_dev, hip_stream);
+}
+
+int dl_eval_fisher_analytic_data(dl_ctx* ctx, const double* centers_dev, int64_t B, const int32_t* data_index_dev, double* hessian_dev, double* gradient_dev,
+                                 double* offset_dev, void* hip_stream) {
+    if (!ctx) { g_last_error = "dl_eval_fisher_analytic_data: null context"; return 1; }
+    if (ctx->n_data_batch == 0) return dl_fail(ctx, "dl_eval_fisher_analytic_data: the context has no data batch (dl_data_set)");
+    if (B < 0) return dl_fail(ctx, "dl_eval_fisher_analytic_data: invalid argument");
+    if (B > 0 && !data_index_dev) return dl_fail(ctx, "dl_eval_fisher_analytic_data: null data index");
+    if (ctx->n_solved > 0) return dl_fail(ctx, "dl_eval_fisher_analytic_data: the context has analytically solved parameters (vary them)");
+    return dl_eval_fisher_analytic_impl(ctx, centers_dev, B, data_index_dev, hessian_dev, gradient_dev, offset_dev, hip_stream);
 }
 
 // Emulated observable (dl_emu_grad.h), per pass of at most 2048 points: theory records (basis, monomial rows) -> U = G . basis (MFMA) -> per point: rows, Gram matrix,
@@ -1267,19 +1319,33 @@ static int dl_eval_logposterior_grad_emu(dl_ctx* ctx, const double* theta_dev, i
 
 // log-posterior and its gradient: theory -> residual rows d~ (direct GEMM) -> chi2 + priors, Y = -d~ W~ (second GEMM) -> gradient workgroups -> chain rule.
 // Returns 2 (nothing launched) when the context is outside the analytic gradient's scope (dl_fullshape_grad.h, dl_emu_grad.h): the caller differentiates numerically.
-int dl_eval_logposterior_grad(dl_ctx* ctx, const double* theta_dev, int64_t B, double* logposterior_dev, double* grad_dev, int32_t* status_dev, void* hip_stream) {
-    if (!ctx) { g_last_error = "dl_eval_logposterior_grad: null context"; return 1; }
-    if (B < 0 || (B > 0 && (!theta_dev || !logposterior_dev || !grad_dev))) return dl_fail(ctx, "dl_eval_logposterior_grad: invalid argument");
-    // emulated: one observable on the feature path, MLP engines (dl_emu_grad.h)
-    const bool emu = ctx->feat_ok && !ctx->any_transform && !ctx->priors_general && ctx->n_obs == 1 && !ctx->any_stacked &&
-                     dl_emu_grad_applicable(ctx->obs_kernarg[0], ctx->N_pad, ctx->n_solved);
-    if (emu) {
+// the emulated branch of dl_eval_logposterior_grad: one observable on the feature path, MLP engines (dl_emu_grad.h)
+static bool dl_grad_emu_in_scope(const dl_ctx* ctx) {
+    return ctx->feat_ok && !ctx->any_transform && !ctx->priors_general && ctx->n_obs == 1 && !ctx->any_stacked &&
+           dl_emu_grad_applicable(ctx->obs_kernarg[0], ctx->N_pad, ctx->n_solved);
+}
+
+// its Kaiser branch (and that of dl_eval_logposterior_grad_data): the gradient kernel's scope (dl_fullshape_grad.h), uniform / Gaussian priors
+static bool dl_grad_kaiser_in_scope(const dl_ctx* ctx) {
+    return !ctx->feat_ok && !ctx->any_transform && ctx->n_solved == 0 && !ctx->priors_general && dl_grad_applicable(ctx->obs_kernarg.data(), ctx->n_obs);
+}
+
+// data_index_dev (dl_eval_logposterior_grad_data; the Kaiser branch only: an emulated context returns 2): point b against vector data_index[b] of the data batch --
+// per pass the RESIDUAL route of dl_eval_impl (tiled split-K window GEMM into delta_ws, no bias), dl_data_paired_kernel for the log-posterior and the status,
+// dl_data_resid_kernel for the rows d~ (dl_data_batch.h) in the place of the chi2 GEMM with the residual output and its finalize; the second GEMM and the gradient
+// kernels do not know.  Null: the launches of dl_eval_logposterior_grad.
+static int dl_eval_logposterior_grad_impl(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, double* logposterior_dev, double* grad_dev,
+                                          int32_t* status_dev, void* hip_stream) {
+    const std::string fn = data_index_dev ? "dl_eval_logposterior_grad_data" : "dl_eval_logposterior_grad";   // (the entry point the messages name)
+    if (!ctx) { g_last_error = fn + ": null context"; return 1; }
+    if (B < 0 || (B > 0 && (!theta_dev || !logposterior_dev || !grad_dev))) return dl_fail(ctx, fn + ": invalid argument");
+    if (dl_grad_emu_in_scope(ctx)) {   // (never with a data index: dl_eval_logposterior_grad_data has returned 2)
         if (B == 0) return 0;
         DL_HIP_CHECK(ctx, hipSetDevice(ctx->device));
         if (dl_order_streams(ctx, (hipStream_t)hip_stream)) return 1;
         return dl_eval_logposterior_grad_emu(ctx, theta_dev, B, logposterior_dev, grad_dev, status_dev, (hipStream_t)hip_stream);
     }
-    if (ctx->feat_ok || ctx->any_transform || ctx->n_solved != 0 || ctx->priors_general || !dl_grad_applicable(ctx->obs_kernarg.data(), ctx->n_obs)) return 2;
+    if (!dl_grad_kaiser_in_scope(ctx)) return 2;
     if (B == 0) return 0;
     hipStream_t stream = (hipStream_t)hip_stream;
     dl_prof_events.start = dl_prof_events.stop = nullptr;
@@ -1317,17 +1383,44 @@ int dl_eval_logposterior_grad(dl_ctx* ctx, const double* theta_dev, int64_t B, d
         const int64_t nb = std::min<int64_t>(per_pass, B - b0);
         const double* th = theta_dev + (size_t)b0 * P;
         int32_t* st = status_dev ? status_dev + b0 : ctx->grad_status;      // (the gradient's finalize needs the status whether the caller wants it or not)
+        if (data_index_dev) {
+            dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, th, P, nb, ctx->power_ws, ctx->K_pad, nullptr, 0, stream, nullptr, 0, 0, ctx->obs_array_dev, false);
+            int cps_r = 0;
+            const int n_slabs_r = dl_gemm_tiled_splits(nb, Np, Kp, &cps_r);   // (nb <= the rows dl_reserve sized delta_ws for: its slab rule is this policy's)
+            const int64_t slab_stride_r = nb * (int64_t)Np;
+            dl_launch_window_gemm_tiled(ctx->power_ws, Kp, ctx->wt_white_dev, Kp, ctx->delta_ws, slab_stride_r, Np, nb, Np, Kp, n_slabs_r, cps_r, stream, ctx->n_white);
+            dl_launch_data_finalize(ctx->delta_ws, Np, ctx->n_white, n_slabs_r, slab_stride_r, ctx->data_bias_dev, Np, ctx->n_data_batch, data_index_dev + b0, th, P, ctx->priors_dev,
+                                    nb, logposterior_dev + b0, st, stream);
+            dl_launch_data_resid(ctx->delta_ws, Np, ctx->n_white, n_slabs_r, slab_stride_r, ctx->data_bias_dev, Np, dl_data_checked(ctx, data_index_dev, B, b0, nb, stream), nb, Np,
+                                 ctx->grad_delta, Np, stream);
+        } else {
         dl_launch_fullshape(ctx->obs_kernarg.data(), ctx->n_obs, th, P, nb, ctx->power_ws, ctx->K_pad, nullptr, 0, stream, nullptr, 0, xcd_local ? dl_chi2_gemm_row_tile(nb, Np) : 0, ctx->obs_array_dev,
                             false);   // (the value from the interval polynomials the gradient kernel differentiates)
         dl_launch_chi2_gemm(ctx->power_ws, Kp, ctx->wt_white_dev, Kp, ctx->bias_white_dev, ctx->delta_ws, nb, Np, Kp, nullptr, nullptr, nullptr, nullptr, nullptr, 1, stream,
                             ctx->panel_ranges.empty() ? nullptr : ctx->panel_ranges.data(), ctx->K_live, ctx->grad_delta, Np, ctx->wt_frag_dev);
         dl_launch_finalize_part(ctx->delta_ws, Np / 16, th, P, ctx->priors_dev, nb, logposterior_dev + b0, nullptr, st, 1, stream);
+        }
         // Y = -d~ W~: [nb, N_pad] x [N_pad, K_pad] through the LDS-DMA tiled GEMM, one split (K = N_pad: 4 panels), no bias
         dl_launch_window_gemm_tiled(ctx->grad_delta, Np, ctx->grad_wtT, Np, ctx->grad_y, 0, Kp, nb, Kp, Np, 1, Np / 16, stream, 0);
         dl_launch_fullshape_grad(ctx->obs_kernarg.data(), ctx->n_obs, ctx->obs_array_dev, th, P, nb, ctx->grad_y, Kp, ctx->grad_phys, ctx->priors_dev, st, grad_dev + (size_t)b0 * P, stream);
     }
     DL_HIP_CHECK(ctx, hipGetLastError());
     return 0;
+}
+
+int dl_eval_logposterior_grad(dl_ctx* ctx, const double* theta_dev, int64_t B, double* logposterior_dev, double* grad_dev, int32_t* status_dev, void* hip_stream) {
+    return dl_eval_logposterior_grad_impl(ctx, theta_dev, B, nullptr, logposterior_dev, grad_dev, status_dev, hip_stream);
+}
+
+int dl_eval_logposterior_grad_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, double* logposterior_dev, double* grad_dev,
+                                   int32_t* status_dev, void* hip_stream) {
+    if (!ctx) { g_last_error = "dl_eval_logposterior_grad_data: null context"; return 1; }
+    if (ctx->n_data_batch == 0) return dl_fail(ctx, "dl_eval_logposterior_grad_data: the context has no data batch (dl_data_set)");
+    if (B > 0 && !data_index_dev) return dl_fail(ctx, "dl_eval_logposterior_grad_data: null data index");
+    if (ctx->n_solved > 0) return dl_fail(ctx, "dl_eval_logposterior_grad_data: the context has analytically solved parameters (vary them)");
+    if (B < 0 || (B > 0 && (!theta_dev || !logposterior_dev || !grad_dev))) return dl_fail(ctx, "dl_eval_logposterior_grad_data: invalid argument");
+    if (!dl_grad_kaiser_in_scope(ctx)) return 2;   // (the emulated branch of the twin solves its solved parameters against the context's own data vector: not with a data batch)
+    return dl_eval_logposterior_grad_impl(ctx, theta_dev, B, data_index_dev, logposterior_dev, grad_dev, status_dev, hip_stream);
 }
 
 int dl_eval_theory(dl_ctx* ctx, const double* theta_dev, int64_t B, int32_t iobs, double* power_dev, double* tables_dev, void* hip_stream) {

@@ -27,27 +27,64 @@
 #define DL_DB_PC 512     // columns staged at a time by a wavefront of the paired kernel (a multiple of DL_DB_NP)
 #define DL_DB_MAX_M 65536
 
-// column j of the residual row before the bias: `col` points at the entry of slab 0
-DL_HD double dl_db_slab_sum(const double* col, int n_slabs, int64_t slab_stride) {
-    double v = 0.;
+// column j of the residual row before the bias: `col` points at the entry of slab 0.  T: double, or the 16-byte pair of columns (j, j + 1) of dl_data_resid_kernel
+// (the same tree on each component; slab_stride in units of T)
+template <typename T>
+DL_HD T dl_db_slab_sum_t(const T* col, int n_slabs, int64_t slab_stride) {
+    T v = (T)0.;
     int sl = 0;
     for (; sl + 8 <= n_slabs; sl += 8) {
-        double t[8];
+        T t[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) t[q] = col[(size_t)(sl + q) * slab_stride];
         v += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
     }
-    double t[8];
+    T t[8];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) t[q] = sl + q < n_slabs ? col[(size_t)(sl + q) * slab_stride] : 0.;
+    for (int q = 0; q < 8; ++q) t[q] = sl + q < n_slabs ? col[(size_t)(sl + q) * slab_stride] : (T)0.;
     v += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
     return v;
 }
 
+DL_HD double dl_db_slab_sum(const double* col, int n_slabs, int64_t slab_stride) { return dl_db_slab_sum_t<double>(col, n_slabs, slab_stride); }
+
+// entry j of the whitened residual row of a (point, data vector) pair from y_bj (dl_db_slab_sum) and bias_mj: the d_j whose squares dl_db_step sums
+template <typename T>
+DL_HD T dl_db_resid(T y, T bias) { return y + bias; }
+
 // one column of one pair: partial sum p of the chain the column belongs to (j % DL_DB_NP)
 DL_HD void dl_db_step(double& p, double y, double bias) {
-    const double d = y + bias;
+    const double d = dl_db_resid(y, bias);
     p = fma(d, d, p);
+}
+
+// Live entry (j < n) of the residual row of a point against data vector m (dl_data_resid_kernel; the analytic derivative paths with a data batch,
+// dl_eval_fisher_analytic_data and dl_eval_logposterior_grad_data): `col` points at the entry of the point in slab 0, `bias` at the entry of the data vector's row of
+// the table, or is NULL for a point whose CHECKED index (dl_data_index_kernel) is -1: NaN, and the table is not read.  T as in dl_db_slab_sum_t.
+template <typename T>
+DL_HD T dl_db_resid_entry(const T* col, int n_slabs, int64_t slab_stride, const T* bias) {
+    if (!bias) return (T)__builtin_nan("");
+    return dl_db_resid(dl_db_slab_sum_t<T>(col, n_slabs, slab_stride), *bias);
+}
+
+// Columns (j, j + 1), j even, of that row as one 16-byte value: the work of one thread of dl_data_resid_kernel.  `row`: the point's row of slab 0; `brow`: the data
+// vector's row of the table, NULL for a checked index of -1.  Columns >= n are exact zeros: the pair at or beyond n reads nothing, the pair that straddles n (n odd)
+// reads both of its columns -- column n < N_pad lies inside the rows -- and zeroes the second.  T2: two doubles .x, .y with + (the device's vector; a struct on the CPU).
+template <typename T2>
+DL_HD T2 dl_db_resid_pair(const double* row, int n_slabs, int64_t slab_stride, const double* brow, int j, int n) {
+    T2 v = (T2)0.;
+    if (j < n) {
+        v = dl_db_resid_entry<T2>(reinterpret_cast<const T2*>(row + j), n_slabs, slab_stride >> 1, brow ? reinterpret_cast<const T2*>(brow + j) : nullptr);
+        if (j + 1 >= n) v.y = 0.;
+    }
+    return v;
+}
+
+// The whole row, column after column: what dl_data_resid_kernel distributes over its lanes, two columns each (tests/csrc/emulate_data_resid.cpp runs this on the
+// CPU).  `row`: the point's row of slab 0; m: its checked index; columns [n, N_pad) are exact zeros (the Gram kernel and the second GEMM of the gradient read them).
+DL_HD void dl_db_resid_row(const double* row, int n_slabs, int64_t slab_stride, const double* bias_tab, int64_t ldb, int m, int n, int N_pad, double* out) {
+    for (int j = 0; j < N_pad; ++j)
+        out[j] = j < n ? dl_db_resid_entry<double>(row + j, n_slabs, slab_stride, m < 0 ? nullptr : bias_tab + (size_t)m * ldb + j) : 0.;
 }
 
 DL_HD double dl_db_tree(const double* p) { return ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7])); }
@@ -206,6 +243,33 @@ __global__ void dl_data_index_kernel(const int32_t* __restrict__ index, int64_t 
     if (b >= B) return;
     const int m = index[b];
     checked[b] = (m >= 0 && m < M) ? m : -1;
+}
+
+// Residual rows of (point, data vector) pairs: resid[b][j] = dl_db_resid_row of point b against data vector checked[b], for the kernels that take d~ as a given row
+// (dl_fisher_kernel<TILES, GIVEN = true>, the second GEMM of the analytic gradient).  One thread per 16 bytes of the output: thread t of the launch owns columns
+// (2 c, 2 c + 1) of row b with b = t / (N_pad / 2), c = t % (N_pad / 2) -- consecutive lanes read consecutive 16 bytes of every slab and of the bias row and write
+// consecutive 16 bytes; a wavefront covers one row of N_pad = 128, so B = 1 is one wavefront of a workgroup whose other three leave at once.  N_pad is even and the
+// rows (ld, slab_stride, ldb, ldr: even, bases from hipMalloc) are 16-byte aligned.  No LDS: every input byte is used once.  Nothing outside [0, B) x [0, N_pad) is
+// read from the slabs or written; columns >= n are written as zeros without a read, the pair that straddles n reads both of its columns (inside the row) and zeroes
+// the second; the table is read for rows with checked[b] >= 0 only.
+__global__ __launch_bounds__(256) void dl_data_resid_kernel(const double* __restrict__ dtilde, int64_t ld, int n, int n_slabs, int64_t slab_stride,
+                                                            const double* __restrict__ bias_tab, int64_t ldb, const int32_t* __restrict__ checked, int64_t B, int N_pad,
+                                                            double* __restrict__ resid, int64_t ldr) {
+    const int half = N_pad >> 1;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t b = t / half;
+    if (b >= B) return;
+    const int j = 2 * (int)(t - b * half);
+    const int m = checked[b];
+    *reinterpret_cast<dl_db_double2*>(resid + (size_t)b * ldr + j) =
+        dl_db_resid_pair<dl_db_double2>(dtilde + (size_t)b * ld, n_slabs, slab_stride, m < 0 ? nullptr : bias_tab + (size_t)m * ldb, j, n);
+}
+
+static void dl_launch_data_resid(const double* dtilde, int64_t ld, int n, int n_slabs, int64_t slab_stride, const double* bias_tab, int64_t ldb, const int32_t* checked,
+                                 int64_t B, int N_pad, double* resid, int64_t ldr, hipStream_t stream) {
+    const int64_t threads = B * (N_pad / 2);
+    DL_LAUNCH(dl_data_resid_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, dtilde, ld, n, n_slabs, slab_stride, bias_tab, ldb, checked, B, N_pad,
+              resid, ldr);
 }
 
 // out: [B, M] (index == nullptr: cross) or [B] (paired)

@@ -264,12 +264,17 @@ __global__ __launch_bounds__(64) void dl_emu_jac_tangent_kernel(const DlObsDev o
 // X = [d~; D~_1 .. D~_P] of one centre per 128-thread workgroup from U [B (1 + n_xv)][19][ldu], the monomials cmono [B][20] and dmono [B][P][20]:
 //   resid [B][ldr]: d~[j] = bias[j] + sum_m c_m U_0m[j] (the order of dl_emu_grad_adjoint_kernel);  rows [B P][ld]: D~_p[j] = sum_m dc_pm U_0m[j] (zero entries skipped)
 //   + sum_{r: col_r == p} sum_m c_m U_(1 + r)m[j].  Each thread owns its columns, every sum runs in index order; columns [n_live, N_pad) are written as zeros.
+// data_index (dl_eval_fisher_analytic_data; null: as above): `bias` is the table [M, ldb] of whitened bias rows of the data batch and the sum of centre b starts from
+// row data_index[b] of it -- CHECKED indices (dl_data_batch.h): -1 starts it from NaN and the table is not read.  The order of the sum is the same.
 __global__ __launch_bounds__(128) void dl_emu_jac_rows_kernel(const DlEjCols cols, const double* __restrict__ U, int64_t ldu, const double* __restrict__ cmono,
                                                               const double* __restrict__ dmono, const double* __restrict__ bias, int n_params, int n_live, int N_pad,
-                                                              double* __restrict__ resid, int64_t ldr, double* __restrict__ rows, int64_t ld, int64_t B) {
+                                                              double* __restrict__ resid, int64_t ldr, double* __restrict__ rows, int64_t ld, int64_t B,
+                                                              const int32_t* __restrict__ data_index, int64_t ldb) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x, n_xv = cols.n_xv;
     const int64_t b = blockIdx.x;
+    const int data_row = data_index ? data_index[b] : 0;
+    const double* brow = data_index ? (data_row >= 0 ? bias + (size_t)data_row * ldb : nullptr) : bias;
     double* c = lds;                          // [20]
     double* dc = lds + DL_FG_MONO_LD;         // [P][20]
     for (int i = tid; i < DL_FG_MONO_LD; i += 128) c[i] = cmono[(size_t)b * DL_FG_MONO_LD + i];
@@ -281,7 +286,7 @@ __global__ __launch_bounds__(128) void dl_emu_jac_rows_kernel(const DlEjCols col
         double um[DL_FG_NM];
 #pragma unroll
         for (int m = 0; m < DL_FG_NM; ++m) um[m] = Ub[(size_t)m * ldu + j];
-        double acc = bias[j];
+        double acc = brow ? brow[j] : __builtin_nan("");
 #pragma unroll
         for (int m = 0; m < DL_FG_NM; ++m) acc = fma(c[m], um[m], acc);
         resid[(size_t)b * ldr + j] = live ? acc : 0.;

@@ -181,6 +181,7 @@ bool dl_emu_jac_applicable(const DlObsDev& obs, int N_pad, int n_params);
 int dl_emu_jac_n_xv(const DlObsDev& obs);   // emulator inputs that are theta columns
 void dl_launch_emu_jac_tangent(const DlObsDev& obs, const double* theta, int n_params, int64_t B, double* basis_rows, double* cmono, double* dmono, hipStream_t stream);
 void dl_launch_emu_jac_rows(const DlObsDev& obs, const double* U, int64_t ldu, const double* cmono, const double* dmono, const double* bias, int n_params, int n_live, int N_pad,
-                            double* resid, int64_t ldr, double* rows, int64_t ld, int64_t B, hipStream_t stream);
+                            double* resid, int64_t ldr, double* rows, int64_t ld, int64_t B, hipStream_t stream,
+                            const int32_t* data_index = nullptr, int64_t ldb = 0);   // data_index [B] (checked: -1 or a row of the table): `bias` is the table [M, ldb] of the data batch (dl_data_batch.h)
 // last-error string of the C ABI (thread-local, read by dl_last_error(NULL)); set by translation units other than dl_api.hip
 void dl_set_last_error(const char* msg);

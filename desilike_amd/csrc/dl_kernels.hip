@@ -2118,10 +2118,11 @@ void dl_launch_emu_jac_tangent(const DlObsDev& obs, const double* theta, int n_p
 }
 
 void dl_launch_emu_jac_rows(const DlObsDev& obs, const double* U, int64_t ldu, const double* cmono, const double* dmono, const double* bias, int n_params, int n_live, int N_pad,
-                            double* resid, int64_t ldr, double* rows, int64_t ld, int64_t B, hipStream_t stream) {
+                            double* resid, int64_t ldr, double* rows, int64_t ld, int64_t B, hipStream_t stream, const int32_t* data_index, int64_t ldb) {
     const DlEjCols cols = dl_ej_cols(obs);
     const size_t shm = (size_t)(1 + n_params) * DL_FG_MONO_LD * sizeof(double);
-    DL_LAUNCH(dl_emu_jac_rows_kernel, dim3((unsigned)B), dim3(128), shm, stream, cols, U, ldu, cmono, dmono, bias, n_params, n_live, N_pad, resid, ldr, rows, ld, B);
+    DL_LAUNCH(dl_emu_jac_rows_kernel, dim3((unsigned)B), dim3(128), shm, stream, cols, U, ldu, cmono, dmono, bias, n_params, n_live, N_pad, resid, ldr, rows, ld, B,
+              data_index, data_index ? ldb : (int64_t)0);
 }
 
 // ---- data batch of a context with analytically solved parameters: per-point records, per-pair solves (dl_data_batch_marg.h) ----

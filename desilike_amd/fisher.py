@@ -147,19 +147,24 @@ class Fisher(object):
 
     def evaluate(self, centers, data_index=None):
         """``centers [B, P]`` (columns ordered as :attr:`varied_params`) -> (offset [B], gradient [B, P], hessian [B, P, P]) of the likelihood term, one GPU batch.
-        ``data_index [B]``: centre b against data vector ``data_index[b]`` of :meth:`set_data_batch` (``dl_eval_fisher_data``: the finite-difference route only)."""
+        ``data_index [B]``: centre b against data vector ``data_index[b]`` of :meth:`set_data_batch` -- ``method='analytic'``: ``dl_eval_fisher_analytic_data``
+        (``NotImplementedError`` outside :attr:`SCOPE`); ``'finite'`` and ``'auto'``: ``dl_eval_fisher_data``, the finite-difference route."""
         import torch
         centers = np.ascontiguousarray(np.atleast_2d(centers), dtype='f8')
         if data_index is not None:
-            if self.method == 'analytic': raise NotImplementedError('the analytic Fisher does not take a data batch: use method="finite"')
             if self._data_ctx is None: raise ValueError('no data batch: call set_data_batch first')
             data_index = np.asarray(data_index)
             if data_index.shape != (centers.shape[0],) or not np.issubdtype(data_index.dtype, np.integer):
                 raise ValueError('data_index must be {:d} integers'.format(centers.shape[0]))
             ctx = self._data_ctx
             device = torch.device('cuda', ctx.device)
-            hessian, gradient, offset = ctx.eval_fisher_data(torch.as_tensor(centers, device=device), torch.as_tensor(self.steps(centers), device=device).contiguous(),
-                                                             torch.as_tensor(np.ascontiguousarray(data_index, dtype='i4'), device=device))
+            index = torch.as_tensor(np.ascontiguousarray(data_index, dtype='i4'), device=device)
+            if self.method == 'analytic':
+                out = ctx.eval_fisher_analytic_data(torch.as_tensor(centers, device=device), index)   # (None: outside the Jacobian kernels' scope, the context decides)
+                if out is None: raise NotImplementedError(self.SCOPE)
+                hessian, gradient, offset = out
+                return offset.cpu().numpy(), gradient.cpu().numpy(), hessian.cpu().numpy()
+            hessian, gradient, offset = ctx.eval_fisher_data(torch.as_tensor(centers, device=device), torch.as_tensor(self.steps(centers), device=device).contiguous(), index)
             return offset.cpu().numpy(), gradient.cpu().numpy(), hessian.cpu().numpy()
         ctx = self._get_context()
         device = torch.device('cuda', ctx.device)

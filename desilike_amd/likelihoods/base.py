@@ -230,6 +230,45 @@ class DataBatch(object):
                 raise ValueError('index must lie in [0, {:d})'.format(self.size))
         return values, index
 
+    GRADIENT_SCOPE = ('the analytic gradient with a data batch covers Kaiser full-shape likelihoods (uniform template knots, no counter terms, no damping, no transform, '
+                      'no solved parameters left in the context) with uniform / norm priors: use method="finite"')
+
+    def logposterior_grad(self, values, index, method='auto'):
+        """``values [B, n_varied]``, ``index [B]`` (integers in ``[0, M)``) -> ``(logposterior [B], gradient [B, n_varied])`` of point b given data vector ``index[b]``.
+        ``method`` as in :func:`desilike_amd.fisher.logposterior_value_and_grad`: ``'analytic'`` -- ``dl_eval_logposterior_grad_data``, the gradient formed on the device
+        from the theory's own derivatives, ``NotImplementedError`` outside its scope (:attr:`GRADIENT_SCOPE`); ``'finite'`` -- central differences of step
+        ``Parameter.delta`` (shortened where a prior bound is closer), the stencil of all points as ONE ``dl_eval_logposterior_data`` batch; ``'auto'`` -- analytic where
+        the context supports it, else finite.  Rows outside the prior get ``-inf`` and, by differences, a NaN gradient.  Batches made with ``solve='point'`` have no
+        gradient (the solved parameters depend on the point and on the data vector): ``NotImplementedError`` before any device call."""
+        import torch
+        if method not in ('auto', 'analytic', 'finite'): raise ValueError('method must be one of auto, analytic, finite')
+        if self.solve == 'point':
+            raise NotImplementedError("logposterior_grad does not take a data batch made with solve='point': analytically solved parameters per point and per data vector have no gradient route")
+        if index is None:
+            raise ValueError('index must be {:d} integers, found None'.format(np.atleast_2d(values).shape[0]))
+        values, index = self._check_values(values, index)
+        B, P = values.shape
+        ctx = self.context
+        device = torch.device('cuda', ctx.device)
+        if method != 'finite':
+            out = ctx.eval_logposterior_grad_data(torch.as_tensor(values, device=device), torch.as_tensor(np.ascontiguousarray(index, dtype='i4'), device=device))
+            if out is not None:      # (None: outside the analytic gradient's scope, the context decides)
+                return out[0].cpu().numpy() + self.offset, out[1].cpu().numpy()
+            if method == 'analytic': raise NotImplementedError(self.GRADIENT_SCOPE)
+        lower, upper = np.empty((B, P)), np.empty((B, P))
+        for ip, param in enumerate(self.likelihood.varied_params):
+            _, lo, hi = param.delta
+            lower[:, ip] = np.clip(np.minimum(lo, values[:, ip] - param.prior.limits[0]), 0., None)
+            upper[:, ip] = np.clip(np.minimum(hi, param.prior.limits[1] - values[:, ip]), 0., None)
+        points = np.repeat(values[:, None, :], 2 * P + 1, axis=1)                 # [B, 1 + 2 P, P]
+        column = np.arange(P)
+        points[:, 1 + 2 * column, column] -= lower
+        points[:, 2 + 2 * column, column] += upper
+        logpost = ctx.eval_logposterior_data_host(points.reshape(-1, P), index=np.repeat(index, 2 * P + 1))[0].reshape(B, 2 * P + 1)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            gradient = (logpost[:, 2::2] - logpost[:, 1::2]) / (lower + upper)
+        return logpost[:, 0] + self.offset, gradient
+
     def solved(self, values, index):
         """``values [B, n_varied]``, ``index [B]`` (integers in ``[0, M)``) -> ``[B, n_solved]``: the analytically solved parameters of point b given data vector
         ``index[b]``, columns ordered as ``likelihood.solved_params`` (``dl_eval_solved_data``).  Batches made with ``solve='point'`` only."""

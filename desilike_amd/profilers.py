@@ -184,9 +184,12 @@ class GaussNewtonProfiler(BasePosteriorSampler):
         ``likelihood.data_batch``) -- "fit every mock" -- from ``nstarts`` starts each: all ``M x nstarts`` starts are rows of ONE Levenberg-Marquardt batch, the data
         vector of a row is its mock (``dl_eval_fisher_data``: the Gauss-Newton curvature does not depend on the data, only the residual does).  ``start``: ``[nstarts, P]``
         (the same starts for every mock) or ``[M, nstarts, P]``, columns ordered as ``self.params``; default: ``nstarts`` draws from the ``ref`` distributions, shared by
-        the mocks.  Solved parameters are varied, as in :meth:`maximize`.  Returns a list of ``M`` :class:`Profiles`."""
+        the mocks.  Solved parameters are varied, as in :meth:`maximize`.  Central differences only: ``derivatives='analytic'`` raises ``NotImplementedError``
+        (the exact derivatives against a data batch are ``Fisher(method='analytic').evaluate(centers, data_index)``).
+        Returns a list of ``M`` :class:`Profiles`."""
         if self.fisher.method == 'analytic':
-            raise NotImplementedError('maximize_batch differentiates by finite differences (the analytic Jacobian route does not take a data batch): use derivatives="finite"')
+            raise NotImplementedError('maximize_batch differentiates by finite differences: use derivatives="finite" (exact derivatives against a data batch: '
+                                      'Fisher(likelihood, method="analytic").evaluate(centers, data_index))')
         M = self.fisher.set_data_batch(data)
         names = [param.name for param in self.params]
         if start is None: start = self._get_start_points(int(nstarts))

@@ -282,6 +282,22 @@ int  dl_eval_fisher_analytic(dl_ctx* ctx, const double* centers_dev, int64_t B, 
  * '.marg' / '.best' solved parameters (dl_emu_grad.h; the log-posterior equals dl_eval_logposterior's to rounding).  Taylor engines, the stacked table layout and
  * several emulated observables return 2. */
 int  dl_eval_logposterior_grad(dl_ctx* ctx, const double* theta_dev, int64_t B, double* logposterior_dev, double* grad_dev, int32_t* status_dev, void* hip_stream);
+/* The exact derivatives against the DATA BATCH (dl_data_set; csrc/dl_data_batch.h): only the residual row d~ of a centre depends on the data, so both calls are their
+ * twins with that row taken against data vector data_index_dev[b] -- the un-biased split-K slabs of the data batch's residual route plus the whitened bias of the
+ * vector, the d_j whose squares dl_eval_logposterior_data sums -- and the derivative rows, the window products, the passes over B and the work buffers of the twins
+ * unchanged.
+ * dl_eval_fisher_analytic_data: outputs and conventions of dl_eval_fisher_analytic (any may be NULL); both of its branches (Kaiser; one emulated observable).  The
+ * Hessian does not depend on the data: it is that of dl_eval_fisher_analytic at the same centres, the same bits.  An index outside [0, M): NaN offset and gradient
+ * for that centre.
+ * dl_eval_logposterior_grad_data: outputs and conventions of dl_eval_logposterior_grad, its Kaiser branch ONLY (an emulated context returns 2: its gradient solves
+ * the solved parameters against the context's own data vector).  The log-posterior is dl_eval_logposterior_data's paired value (theory without the moment form, as
+ * in dl_eval_logposterior_grad).  An index outside [0, M): NaN log-posterior and DL_STATUS_NAN_INPUT, and the gradient row of a point of that status.
+ * Both return 1 -- before any launch -- for a NULL context, a context without a data batch, a NULL index with B > 0 or a context with analytically solved
+ * parameters; 2 -- nothing launched -- outside the scope stated above of their twins.  Asynchronous on ``hip_stream``. */
+int  dl_eval_fisher_analytic_data(dl_ctx* ctx, const double* centers_dev, int64_t B, const int32_t* data_index_dev, double* hessian_dev, double* gradient_dev,
+                                  double* offset_dev, void* hip_stream);
+int  dl_eval_logposterior_grad_data(dl_ctx* ctx, const double* theta_dev, int64_t B, const int32_t* data_index_dev, double* logposterior_dev, double* grad_dev,
+                                    int32_t* status_dev, void* hip_stream);
 
 /* Theory state of observable ``iobs`` for parity / plots / emulation:
  * power_dev [B, n_ell, n_kin] and (optional) tables_dev [B, 3, n_ell, n_kin] = pk_dd, pk_dt, pk_tt. */
